@@ -1,6 +1,7 @@
 """GAN train-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--batch 16]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 A step = the fused HIP train step (G forward, D fwd/bwd on [real; fake], D
@@ -9,8 +10,14 @@ synthetic 256x256 batch of 16 IR/RGB pairs per GPU, bf16 operands with fp32
 accumulation, random-init weights of the reference architecture.  Weak scaling:
 every rank trains on its own 16-pair shard and all-reduces grads (RCCL).
 
-Prints ONE JSON line (rank 0) with the metric, a live roofline for the dominant
-conv kernel (HIP events around its launches) and the CPU-oracle baseline.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0)
+with the metric.  ``--dump-outputs DIR`` also writes what the last timed step
+computed (dump_outputs) and makes the whole run bit-reproducible (the steps take
+the deterministic weight-gradient reductions; ``deterministic`` in the line).
+``--full`` adds, after the timed region, what takes runs of its own: a live
+roofline for the dominant conv kernel (HIP events around its launches in
+--kernel-steps extra steps), the measured MFMA peak, the default weight-gradient
+reduction checked against the deterministic one, and the CPU-oracle baseline.
 """
 from __future__ import annotations
 
@@ -173,6 +180,132 @@ def cpu_baseline(H, W, batch=16, budget_s=12.0, min_steps=3):
                       f"granted to the process ({ncpu} host CPUs, {_cpu_model()})"}
 
 
+DUMP_MAX_ELEMS = 4 << 20   # per array: 16 MB of float32, so the three arrays stay far below 64 MB
+
+
+def dump_outputs(dirname, tr, L):
+    """What a caller of the timed path holds after its last step, as float32 / float64 .npy files:
+
+    * ``losses.npy``: the loss vector ``GANTrainer.step`` returned (float64; GANStep's slots);
+    * ``fake.npy``: the generator's output of that step (float32, NHWC, flattened);
+    * ``netG_params.npy``, ``netD_params.npy``: the parameters the step's two Adam updates left,
+      every tensor of the state dict in its order and OIHW layout, flattened and concatenated
+      (float32).
+
+    An array above DUMP_MAX_ELEMS elements is cut to a fixed sample of that many
+    (sorted indices of a randperm seeded with the array's length), the same in every run.
+    The inputs and initial weights are seeded and a dumping run steps in deterministic mode
+    (main), so two runs with the same arguments write the same parameters bit for bit (the
+    losses are fp64 atomic block sums: equal to ~1e-12 relative), and two builds can be
+    compared file by file."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"losses": L.detach().to("cpu", torch.float64),
+              "fake": tr.netG.engine.bufs.d["fake"].detach().to("cpu", torch.float32).reshape(-1)}
+    for name, net in (("netG_params", tr.netG), ("netD_params", tr.netD)):
+        arrays[name] = torch.cat([v.detach().to("cpu", torch.float32).reshape(-1)
+                                  for v in net.store.state().values()])
+    for name, flat in arrays.items():
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(flat.numel())
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            flat = flat[idx]
+        np.save(os.path.join(dirname, name + ".npy"), flat.contiguous().numpy())
+
+
+def reduction_check(tr, ir, rgb, ops):
+    """--full: one more step from the same state under each weight-gradient reduction -- the
+    default one (fp32 atomics across the K splits: what a run without --dump-outputs times) and
+    the deterministic one (ordered slabs: what a dumping run times and dumps) -- and the
+    relative L2 distance of the two gradients per network.  Same state, same inputs: the
+    activations are identical and only the order (and number) of the fp32 partial sums of each
+    dW element differs, so the figures are fp32 summation noise; anything larger means the two
+    paths no longer compute the same gradients and the dumps stop vouching for the timed path."""
+    import torch
+    sd = tr.state_dict()
+    grads, old = {}, ops.set_deterministic(False)
+    try:
+        for det in (False, True):
+            tr.load_state_dict(sd)
+            ops.set_deterministic(det)
+            tr.step(ir, rgb)
+            torch.cuda.synchronize()
+            grads[det] = {n: getattr(tr, n).store.grad.double().clone() for n in ("netG", "netD")}
+    finally:
+        ops.set_deterministic(old)
+    return {f"{n}_grad_rel_l2": float((grads[False][n] - grads[True][n]).norm() / grads[True][n].norm())
+            for n in ("netG", "netD")}
+
+
+def roofline_report(ops, args, timing, res_tags, ring_tag, hbm_bytes, B, H, W):
+    """--full: the roofline of the dominant kernel family (algorithmic FLOPs per launch / mean
+    launch time from the --kernel-steps steps' HIP events), the HBM-bound passes, the committed
+    PMC traffic figure and the MFMA peak measured now (mfma_peak_measured)."""
+    res_flop = 2.0 * B * (H // 4) * (W // 4) * 256 * 256 * 9
+
+    def peak_of(tag):
+        if args.dtype == "fp32":
+            return FP32_MFMA_PEAK_TFLOPS
+        return FP8_DENSE_PEAK_TFLOPS if tag.split(":")[0].endswith("8") else BF16_DENSE_PEAK_TFLOPS
+    kern = {}
+    for tg in res_tags:
+        if tg in timing:
+            n, mean_ms = timing[tg]
+            kern[tg] = {"launches": n, "mean_ms": round(mean_ms, 4),
+                        "tflops": round(res_flop / (mean_ms * 1e-3) / 1e12, 2), "peak": peak_of(tg)}
+    dom = max(kern, key=lambda k: kern[k]["launches"] * kern[k]["mean_ms"]) if kern else None
+    ring = None
+    if ring_tag in timing:   # off the critical path: beside the wgrad on the side stream
+        n, mean_ms = timing[ring_tag]
+        ring = {"launches": n, "mean_ms": round(mean_ms, 4), "stream": "side (under the weight gradient)"}
+        dg = [t for t in kern if t.startswith("dgrad:")]
+        if dg:
+            tot = kern[dg[0]]["mean_ms"] + mean_ms
+            ring["dgrad_plus_ring_ms"] = round(tot, 4)
+            ring["dgrad_plus_ring_tflops"] = round(res_flop / (tot * 1e-3) / 1e12, 2)
+    hbm = {}
+    nel = B * (H // 4) * (W // 4) * 256
+    for tg, bpe in hbm_bytes.items():
+        if tg in timing:
+            n, mean_ms = timing[tg]
+            hbm[tg] = {"launches": n, "mean_ms": round(mean_ms, 4), "alg_bytes": bpe * nel,
+                       "gbps": round(bpe * nel / (mean_ms * 1e-3) / 1e9, 1),
+                       "frac_of_8tbs": round(bpe * nel / (mean_ms * 1e-3) / 8e12, 4)}
+    achieved = kern[dom]["tflops"] if dom else None
+    peak = peak_of(dom) if dom else BF16_DENSE_PEAK_TFLOPS
+    traffic = pmc_traffic(dom.split(":")[0]) if (dom and H == 256 and B == 16 and args.dtype == "bf16") else None
+    mp = mfma_peak_measured(ops) if args.dtype != "fp32" else None
+    # fp8 (block-scaled f8f6f4, 32x32x64): the cycles of the bf16 32x32x16 at 4x the K, i.e. 2x
+    # the bf16 rate per clock, so its measured peak is 2x the bf16 probe
+    mpeak = (2 * mp if (dom or "").split(":")[0].endswith("8") else mp) if mp else None
+    return {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4) if achieved else None, "traffic": traffic,
+            "peak_measured": mpeak, "frac_of_measured_peak": round(achieved / mpeak, 4)
+            if (achieved and mpeak) else None,
+            "peak_measured_note": "irgan_mfma_probe: back-to-back bf16 16x16x32 MFMAs on random "
+                                  "operands, every SIMD 4 waves deep, no memory traffic (the rate the "
+                                  "box sustains under MFMA load); fp8: 2x that (f8f6f4 cycles per "
+                                  "FLOP); `peak` stays the nominal dense figure",
+            "traffic_unit": "HBM bytes per launch (rocprofv3 PMC: 2*FETCH_SIZE + WRITE_SIZE, "
+                            f"{os.path.relpath(pmc_file(), ROOT) if pmc_file() else 'none'})",
+            "flop_per_launch": res_flop, "per_kernel": kern,
+            "kernel_timing": f"HIP events around each tagged launch on its stream, {args.kernel_steps} "
+                             "steps right after the timed region (same process, inputs and "
+                             "buffers); the timed region itself carries no per-kernel events",
+            "reflect_ring": ring,
+            "ring_note": "dgrad = the backward-data launch on the main stream; with reflect_ring "
+                         "set, the reflect-pad ring of each ResnetBlock dgrad (the fold of the padded "
+                         "border, 6% of the FLOPs) runs as its own launches on the side stream, "
+                         "concurrently with that conv's weight gradient (which leaves 16 CUs idle)",
+            "hbm_kernels": hbm,
+            "hbm_note": "InstanceNorm passes at the resblock shape, HIP events on the launching "
+                        "stream; alg_bytes = bf16 bytes read + written once (in_bwd_reduce: dy, z; "
+                        "_apply: dy, z, dx; in_apply: z, y; _res: + residual); in_bwd_reduce "
+                        "includes its finalize launch"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -184,10 +317,16 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="per-GPU batch")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
                     help="fp8: BASELINE configs[4] -- the ResnetBlock convs on e4m3 operands (use --batch 32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs); the "
+                         "run then steps in deterministic mode (ordered weight-gradient reductions)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the per-kernel roofline (--kernel-steps), the "
+                         "MFMA peak and the CPU-oracle baseline; a plain run prints the metric only")
     ap.add_argument("--kernel-steps", type=int, default=5,
-                    help="steps after the timed region with per-kernel HIP events (roofline lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds per CPU thread-count run")
+                    help="--full: steps after the timed region with per-kernel HIP events (roofline lines)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU-oracle leg")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds per CPU thread-count run")
     args = ap.parse_args()
 
     import torch
@@ -202,6 +341,25 @@ def main():
     irc = importlib.import_module(PKG)
     ops = irc.ops
 
+    # the default step reduces its split-K weight gradients with fp32 atomics, whose order
+    # differs from run to run (and the GAN's dynamics amplify that within a few steps), so a
+    # run that dumps its outputs takes the step's deterministic mode (ops.set_deterministic:
+    # ordered slab reductions), in which the whole run is reproducible bit for bit; --full
+    # checks the two reductions against each other (reduction_check)
+    det_old = ops.set_deterministic(bool(args.dump_outputs))
+    try:
+        run(args, irc, world, rank, local)
+    finally:
+        ops.set_deterministic(det_old)
+        if world > 1:
+            dist.destroy_process_group()
+
+
+def run(args, irc, world, rank, local):
+    """Set-up, warm-up, the timed steps, the dump and the result line of one rank."""
+    import torch
+    import torch.distributed as dist
+    ops = irc.ops
     H = args.height or args.size
     W = args.width or args.size
     B = args.batch
@@ -251,12 +409,15 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    # per-kernel HIP events on the launching streams, same inputs, right after the timed region
-    ops.TIMER.enabled = True
-    for _ in range(args.kernel_steps):
-        tr.step(ir, rgb)
-    torch.cuda.synchronize()
-    ops.TIMER.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, L)
+    if args.full:
+        # per-kernel HIP events on the launching streams, same inputs, right after the timed region
+        ops.TIMER.enabled = True
+        for _ in range(args.kernel_steps):
+            tr.step(ir, rgb)
+        torch.cuda.synchronize()
+        ops.TIMER.enabled = False
     el_min = el
     replicas_ok = True
     if world > 1:
@@ -267,99 +428,40 @@ def main():
         el, el_min = float(t), float(tmin)
         # every rank must still hold bit-identical G and D after the timed steps
         replicas_ok = irc.engine.replicas_identical([tr.netG.store.flat, tr.netD.store.flat])
-    timing = ops.TIMER.summary()
+    timing = ops.TIMER.summary() if args.full else {}
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2]
     losses = tr.losses(L)
+    reductions = reduction_check(tr, ir, rgb, ops) if args.full and world == 1 else None
 
     if rank == 0:
         imgs = B * world * args.steps
         value = imgs / el
         ms = el / args.steps * 1e3
-        # roofline of the dominant kernel family: algorithmic FLOPs per launch / mean launch time
-        res_flop = 2.0 * B * (H // 4) * (W // 4) * 256 * 256 * 9
-        def peak_of(tag):
-            if args.dtype == "fp32":
-                return FP32_MFMA_PEAK_TFLOPS
-            return FP8_DENSE_PEAK_TFLOPS if tag.split(":")[0].endswith("8") else BF16_DENSE_PEAK_TFLOPS
-        kern = {}
-        for tg in res_tags:
-            if tg in timing:
-                n, mean_ms = timing[tg]
-                kern[tg] = {"launches": n, "mean_ms": round(mean_ms, 4),
-                            "tflops": round(res_flop / (mean_ms * 1e-3) / 1e12, 2), "peak": peak_of(tg)}
-        dom = max(kern, key=lambda k: kern[k]["launches"] * kern[k]["mean_ms"]) if kern else None
-        ring = None
-        if ring_tag in timing:   # off the critical path: beside the wgrad on the side stream
-            n, mean_ms = timing[ring_tag]
-            ring = {"launches": n, "mean_ms": round(mean_ms, 4), "stream": "side (under the weight gradient)"}
-            dg = [t for t in kern if t.startswith("dgrad:")]
-            if dg:
-                tot = kern[dg[0]]["mean_ms"] + mean_ms
-                ring["dgrad_plus_ring_ms"] = round(tot, 4)
-                ring["dgrad_plus_ring_tflops"] = round(res_flop / (tot * 1e-3) / 1e12, 2)
-        hbm = {}
-        nel = B * (H // 4) * (W // 4) * 256
-        for tg, bpe in hbm_bytes.items():
-            if tg in timing:
-                n, mean_ms = timing[tg]
-                hbm[tg] = {"launches": n, "mean_ms": round(mean_ms, 4), "alg_bytes": bpe * nel,
-                           "gbps": round(bpe * nel / (mean_ms * 1e-3) / 1e9, 1),
-                           "frac_of_8tbs": round(bpe * nel / (mean_ms * 1e-3) / 8e12, 4)}
-        achieved = kern[dom]["tflops"] if dom else None
-        peak = peak_of(dom) if dom else BF16_DENSE_PEAK_TFLOPS
-        traffic = pmc_traffic(dom.split(":")[0]) if (dom and H == 256 and B == 16 and args.dtype == "bf16") else None
-        mp = mfma_peak_measured(ops) if args.dtype != "fp32" else None
-        # fp8 (block-scaled f8f6f4, 32x32x64): the cycles of the bf16 32x32x16 at 4x the K, i.e. 2x
-        # the bf16 rate per clock (MI355X_MICROARCH.md), so its measured peak is 2x the bf16 probe
-        mpeak = (2 * mp if (dom or "").split(":")[0].endswith("8") else mp) if mp else None
         step_tflops = value * min_gflop_per_img(H, W) / 1e3 / world
         out = {
             "metric": METRIC, "value": round(value, 3), "unit": "img/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 3),
             "ms_per_step_median": round(median_ms, 3), "img_per_s_median_step": round(B * world / median_ms * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak",
+            "higher_is_better": True, "scaling": "weak", "deterministic": bool(args.dump_outputs),
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic (U(-1,1) IR/RGB pairs, seeded; random-init weights)",
             "config": {"workload": workload_label(H, W, B, args.dtype, world), "global_batch": B * world,
                        "img_size": H, "height": H, "width": W, "parallelism": f"dp{world}",
                        "min_gflop_per_img": round(min_gflop_per_img(H, W), 2),
                        "step_tflops_per_gpu": round(step_tflops, 2),
                        "step_frac_of_bf16_peak": round(step_tflops / BF16_DENSE_PEAK_TFLOPS, 4)},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4) if achieved else None, "traffic": traffic,
-                         "peak_measured": mpeak, "frac_of_measured_peak": round(achieved / mpeak, 4)
-                         if (achieved and mpeak) else None,
-                         "peak_measured_note": "irgan_mfma_probe: back-to-back bf16 16x16x32 MFMAs on random "
-                                               "operands, every SIMD 4 waves deep, no memory traffic (the rate the "
-                                               "box sustains under MFMA load); fp8: 2x that (f8f6f4 cycles per "
-                                               "FLOP); `peak` stays the nominal dense figure",
-                         "traffic_unit": "HBM bytes per launch (rocprofv3 PMC: 2*FETCH_SIZE + WRITE_SIZE, "
-                                         f"{os.path.relpath(pmc_file(), ROOT) if pmc_file() else 'none'})",
-                         "flop_per_launch": res_flop, "per_kernel": kern,
-                         "kernel_timing": f"HIP events around each tagged launch on its stream, {args.kernel_steps} "
-                                          "steps right after the timed region (same process, inputs and "
-                                          "buffers); the timed region itself carries no per-kernel events",
-                         "reflect_ring": ring,
-                         "ring_note": "dgrad = the backward-data launch on the main stream; with reflect_ring "
-                                      "set, the reflect-pad ring of each ResnetBlock dgrad (the fold of the padded "
-                                      "border, 6% of the FLOPs) runs as its own launches on the side stream, "
-                                      "concurrently with that conv's weight gradient (which leaves 16 CUs idle)",
-                         "hbm_kernels": hbm,
-                         "hbm_note": "InstanceNorm passes at the resblock shape, HIP events on the launching "
-                                     "stream; alg_bytes = bf16 bytes read + written once (in_bwd_reduce: dy, z; "
-                                     "_apply: dy, z, dx; in_apply: z, y; _res: + residual); in_bwd_reduce "
-                                     "includes its finalize launch"},
             "dp": {"rccl_world": world, "backend": dist.get_backend() if world > 1 else None,
                    "rank_time_s": {"max": round(el, 4), "min": round(el_min, 4)},
                    "replicas_bit_identical": replicas_ok},
             "losses": {k: round(v, 5) for k, v in losses.items()},
             **(step_phases(irc.engine.JOIN_TIMES[-args.steps:]) if irc.engine.JOIN_TIMES else {}),
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(H, W, B, args.cpu_budget)
+        if args.full:
+            out["roofline"] = roofline_report(ops, args, timing, res_tags, ring_tag, hbm_bytes, B, H, W)
+            out["reduction_check"] = reductions
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(H, W, B, args.cpu_budget)
         print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 def workload_label(H, W, B, dtype, world):

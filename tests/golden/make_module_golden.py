@@ -14,7 +14,7 @@ Every case runs in fp64 on seeded inputs and weights (oracle.seeded_params, so t
 tests rebuild the same weights from the seeds) and stores the module output and the
 gradients of the scalar objective sum(out * R) (R seeded): parameter gradients as
 sampled digests (64 entries + the norm per tensor), D / SSIM input gradients in full.
-Output: tests/golden/modules.npz.
+Output: tests/golden/modules_{g,d_a,d_b,ssim}.npz.
 """
 from __future__ import annotations
 
@@ -41,6 +41,16 @@ G_CASES = {
 }
 D_CASES = {"d_n1": (1, "instance"), "d_n2": (2, "instance"), "d_n4": (4, "instance"), "d_none": (3, "none")}
 SSIM_WINDOWS = (3, 5, 7)
+
+
+def part_of(key):
+    """The file a record goes to: one per case family, the D cases in two, so that each
+    file stays below 1 MiB (the tests merge modules_*.npz)."""
+    if key.startswith("g_"):
+        return "g"
+    if key.startswith("ssim"):
+        return "ssim"
+    return "d_a" if key.split("|")[0] in ("d_x", "d_n1", "d_n2") else "d_b"
 
 
 def main():
@@ -102,9 +112,13 @@ def main():
             (loss * w).sum().backward()
             rec[f"ssim{ws}_{int(avg)}|loss"] = loss.detach().numpy()
             rec[f"ssim{ws}_{int(avg)}|grad"] = aa.grad.numpy()
-    out = os.path.join(HERE, "modules.npz")
-    np.savez_compressed(out, **rec)
-    print("wrote", out, os.path.getsize(out), "bytes")
+    parts = {}
+    for k, v in rec.items():
+        parts.setdefault(part_of(k), {})[k] = v
+    for p, sub in parts.items():
+        out = os.path.join(HERE, f"modules_{p}.npz")
+        np.savez_compressed(out, **sub)
+        print("wrote", out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":

@@ -11,11 +11,11 @@ if [ -n "$T" ]; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo ALLDONE; exit 0; fi
 fi
 for rep in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_default_$rep.json 2> $O/bench_default_$rep.err || { echo "bench default failed"; break; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_default_$rep.json 2> $O/bench_default_$rep.err || { echo "bench default failed"; break; }
   python -c "import json; d=json.load(open('$O/bench_default_$rep.json')); print('default', d['value'], {k.split(':')[0]: v['mean_ms'] for k, v in d['roofline']['per_kernel'].items()})"
   for envs in "$@"; do
     tag=$(echo $envs | tr ' =' '__')
-    timeout -k 10 300 env $envs python bench.py --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; break 2; }
+    timeout -k 10 300 env $envs python bench.py --full --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; break 2; }
     python -c "import json; d=json.load(open('$O/bench_${tag}_$rep.json')); print('$envs', d['value'], {k.split(':')[0]: v['mean_ms'] for k, v in d['roofline']['per_kernel'].items()})"
   done
 done

@@ -9,7 +9,7 @@ for rep in 1 2; do
   for arm in "$@"; do
     i=$((i+1))
     if [ "$arm" = "-" ]; then E=""; else E="$arm"; fi
-    env $E timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline $BENCH_EXTRA > $O/arm${i}_$rep.json 2> $O/arm${i}_$rep.err || { echo "arm $i failed"; tail -3 $O/arm${i}_$rep.err; exit 1; }
+    env $E timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline $BENCH_EXTRA > $O/arm${i}_$rep.json 2> $O/arm${i}_$rep.err || { echo "arm $i failed"; tail -3 $O/arm${i}_$rep.err; exit 1; }
     python -c "import json; d=json.load(open('$O/arm${i}_$rep.json')); print('arm $i ($arm) rep $rep', d['value'], d['ms_per_step'])"
   done
 done

@@ -20,7 +20,7 @@ done
 for rep in 1 2; do
   for v in default "$@"; do
     L=""; [ $v != default ] && L=$B/libirgan_$v.so
-    IRGAN_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || { echo "bench $v failed"; echo ALLDONE; exit 0; }
+    IRGAN_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || { echo "bench $v failed"; echo ALLDONE; exit 0; }
     python -c "import json; d=json.load(open('$O/bench_${v}_$rep.json')); print('$v', d['value'], d['ms_per_step_median'], {k.split(':')[0]: v['mean_ms'] for k, v in d['roofline']['per_kernel'].items()})"
   done
 done

@@ -10,6 +10,6 @@ timeout -s KILL 90 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAIT_INST_LDS SQ_LDS_UNALIGNED_STALL SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA GRBM_GUI_ACTIVE -d $O/sq2 -o run --output-format csv -- $MB > $O/sq2.log 2>&1 || echo "sq2 failed" >> $O/sq2.log
 timeout -s KILL 90 rocprofv3 --pmc FETCH_SIZE -d $O/fetch_mb -o run --output-format csv -- $MB > $O/fetch_mb.log 2>&1
 timeout -s KILL 90 rocprofv3 --pmc WRITE_SIZE -d $O/write_mb -o run --output-format csv -- $MB > $O/write_mb.log 2>&1
-timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d $O/fetch_bench -o run --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch_bench.log 2>&1
-timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d $O/write_bench -o run --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/write_bench.log 2>&1
+timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d $O/fetch_bench -o run --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/fetch_bench.log 2>&1
+timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d $O/write_bench -o run --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/write_bench.log 2>&1
 echo ALLDONE

@@ -9,10 +9,10 @@ if [ -n "$2" ]; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit 0; fi
 fi
 for rep in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_$rep.json 2> $O/bench_$rep.err || { echo "bench failed"; exit 0; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_$rep.json 2> $O/bench_$rep.err || { echo "bench failed"; exit 0; }
   python -c "import json; d=json.load(open('$O/bench_$rep.json')); print('bench', d['value'], {k.split(':')[0]: v['mean_ms'] for k, v in d['roofline']['per_kernel'].items()})"
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --kernel-steps 1 --no-cpu-baseline > $O/prof.log 2>&1 || { echo "rocprof failed"; exit 0; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --full --steps 5 --warmup 2 --kernel-steps 1 --no-cpu-baseline > $O/prof.log 2>&1 || { echo "rocprof failed"; exit 0; }
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python tools/prof_summary.py $T --steps 8 > $O/summary.md && python tools/prof_summary.py $T --steps 8 --by-grid > $O/summary_by_grid.md
 head -30 $O/summary.md

@@ -12,13 +12,13 @@ echo "== bn old"; grep "ms/TFLOPs" $O/mb_bnold.txt
 for rep in 1 2; do
   for envs in "IRGAN_NONE=1" "IRGAN_R64_PATCH_STATS=1" "IRGAN_NO_POOL_FUSION=1" "IRGAN_R64_PATCH_STATS=1 IRGAN_NO_POOL_FUSION=1"; do
     tag=$(echo $envs | tr ' =' '__')
-    timeout -k 10 300 env $envs python bench.py --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; exit 1; }
+    timeout -k 10 300 env $envs python bench.py --full --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; exit 1; }
     python -c "import json; d=json.load(open('$O/bench_${tag}_$rep.json')); print('$envs', d['value'], d['ms_per_step_median'])"
   done
 done
-IRGAN_LIB=$P/variants/libirgan_bn_old.so timeout -k 10 300 python bench.py --height 512 --width 640 --batch 4 --no-cpu-baseline > $O/bench_512_bnold.json 2> $O/bench_512_bnold.err || { echo bench512old failed; exit 1; }
+IRGAN_LIB=$P/variants/libirgan_bn_old.so timeout -k 10 300 python bench.py --full --height 512 --width 640 --batch 4 --no-cpu-baseline > $O/bench_512_bnold.json 2> $O/bench_512_bnold.err || { echo bench512old failed; exit 1; }
 echo "bench512 bnold $(python -c "import json; d=json.load(open('$O/bench_512_bnold.json')); print(d['value'], d['ms_per_step_median'], {k: v['mean_ms'] for k, v in d['roofline']['per_kernel'].items()})")"
-timeout -k 10 300 python bench.py --height 512 --width 640 --batch 4 --no-cpu-baseline > $O/bench_512.json 2> $O/bench_512.err || { echo bench512 failed; exit 1; }
+timeout -k 10 300 python bench.py --full --height 512 --width 640 --batch 4 --no-cpu-baseline > $O/bench_512.json 2> $O/bench_512.err || { echo bench512 failed; exit 1; }
 echo "bench512 $(python -c "import json; d=json.load(open('$O/bench_512.json')); print(d['value'], d['ms_per_step_median'], {k: v['mean_ms'] for k, v in d['roofline']['per_kernel'].items()})")"
 bash tools/gpu_trace.sh r06_c/trace
 echo ALLDONE

@@ -11,7 +11,7 @@ grep "ms/TFLOPs" $O/mb_default.txt
 for rep in 1 2 3; do
   for envs in "IRGAN_NONE=1" "IRGAN_D_WGRAD_SIDE=1" "IRGAN_NO_POOL_FUSION=1"; do
     tag=$(echo $envs | tr ' =' '__')
-    IRGAN_JOIN_TIMING=1 timeout -k 10 300 env $envs python bench.py --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; exit 1; }
+    IRGAN_JOIN_TIMING=1 timeout -k 10 300 env $envs python bench.py --full --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; exit 1; }
     python -c "import json; d=json.load(open('$O/bench_${tag}_$rep.json')); print('$envs', d['value'], d['ms_per_step_median'], 'join_wait', d.get('join_wait_ms'), d.get('step_phase_ms'))"
   done
 done

@@ -11,7 +11,7 @@ echo "== new"; grep " us " $O/rs_new.txt; echo "== old"; grep " us " $O/rs_old.t
 for rep in 1 2 3; do
   for envs in "IRGAN_NONE=1" "IRGAN_SEP_ROWS1=1"; do
     tag=$(echo $envs | tr ' =' '__')
-    timeout -k 10 300 env $envs python bench.py --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; exit 1; }
+    timeout -k 10 300 env $envs python bench.py --full --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err || { echo "bench $envs failed"; exit 1; }
     python -c "import json; d=json.load(open('$O/bench_${tag}_$rep.json')); print('$envs', d['value'], d['ms_per_step_median'])"
   done
 done

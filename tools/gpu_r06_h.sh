@@ -7,8 +7,8 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_dgrad_inred.py tests/test_g
 rc=$?; echo "pytest rc=$rc $(tail -1 $O/pytest.log)"
 [ $rc -ne 0 ] && { grep -E "^FAILED|Error|assert" $O/pytest.log | head -20; exit 1; }
 for r in 1 2 3; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_on_$r.json 2> $O/bench_on_$r.err || { echo "on $r failed"; exit 1; }
-  IRGAN_NO_DGRAD_INRED=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_off_$r.json 2> $O/bench_off_$r.err || { echo "off $r failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_on_$r.json 2> $O/bench_on_$r.err || { echo "on $r failed"; exit 1; }
+  IRGAN_NO_DGRAD_INRED=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_off_$r.json 2> $O/bench_off_$r.err || { echo "off $r failed"; exit 1; }
 done
 python - <<PY
 import json

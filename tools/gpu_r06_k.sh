@@ -5,6 +5,6 @@ timeout -k 10 1200 python -u -m pytest tests -m gpu -q -rP --timeout 300 --timeo
 rc=$?; echo "pytest rc=$rc $(tail -1 $O/pytest_gpu.log)"
 [ $rc -ne 0 ] && { grep -E "^FAILED" $O/pytest_gpu.log | head; exit 1; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc=$? $(tail -1 $O/smoke.log)"
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo bench failed; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo bench failed; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); print('bench', d['value'], d['ms_per_step_median'], d['roofline']['frac'])"
 echo ALLDONE

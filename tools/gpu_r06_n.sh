@@ -18,8 +18,8 @@ for v in 0 1 0 1; do
   echo "W3=$v: $(tail -2 $O/mb_$v.txt | tr '\n' ' ')"
 done
 for r in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_w2_$r.json 2>/dev/null || { echo bench failed; exit 1; }
-  IRGAN_W3=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_w3_$r.json 2>/dev/null || { echo bench w3 failed; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_w2_$r.json 2>/dev/null || { echo bench failed; exit 1; }
+  IRGAN_W3=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_w3_$r.json 2>/dev/null || { echo bench w3 failed; exit 1; }
 done
 python - <<PY
 import json

@@ -24,8 +24,8 @@ PY
 timeout -k 10 120 python $O/mp.py > $O/mp_rows.txt 2>&1 && IRGAN_NO_POOL_ROWS=1 timeout -k 10 120 python $O/mp.py > $O/mp_old.txt 2>&1 || { echo mp failed; exit 1; }
 echo rows; cat $O/mp_rows.txt; echo old; cat $O/mp_old.txt
 for r in 1 2 3; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_on_$r.json 2>/dev/null || { echo "on $r failed"; exit 1; }
-  IRGAN_NO_POOL_ROWS=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_off_$r.json 2>/dev/null || { echo "off $r failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_on_$r.json 2>/dev/null || { echo "on $r failed"; exit 1; }
+  IRGAN_NO_POOL_ROWS=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_off_$r.json 2>/dev/null || { echo "off $r failed"; exit 1; }
 done
 python - <<PY
 import json

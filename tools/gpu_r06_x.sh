@@ -8,9 +8,9 @@ rc=$?; echo "pytest rc=$rc $(tail -1 $O/pytest.log)"
 IRGAN_NO_D_OVERLAP=1 timeout -k 10 300 python tools/layer_times.py > $O/layer_times_serial.txt 2>&1 || { echo lt failed; exit 1; }
 grep -E "512x1k4" $O/layer_times_serial.txt
 for r in 1 2 3; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_on_$r.json 2>/dev/null || { echo "on $r failed"; exit 1; }
-  IRGAN_NO_HEAD_WGRAD=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_nowg_$r.json 2>/dev/null || { echo "nowg $r failed"; exit 1; }
-  IRGAN_NO_PATCH_HEAD=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_off_$r.json 2>/dev/null || { echo "off $r failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_on_$r.json 2>/dev/null || { echo "on $r failed"; exit 1; }
+  IRGAN_NO_HEAD_WGRAD=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_nowg_$r.json 2>/dev/null || { echo "nowg $r failed"; exit 1; }
+  IRGAN_NO_PATCH_HEAD=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_off_$r.json 2>/dev/null || { echo "off $r failed"; exit 1; }
 done
 python - <<PY
 import json

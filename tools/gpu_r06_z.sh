@@ -12,8 +12,8 @@ IRGAN_HEAD_FWD_FUSED=1 timeout -k 10 120 rocprofv3 --kernel-trace --stats -d $O/
 timeout -k 10 120 rocprofv3 --kernel-trace --stats -d $O/prof_split -o run --output-format csv -- python3 tools/head_prof.py > $O/prof_split.log 2>&1 || { echo prof2 failed; exit 1; }
 python tools/kernel_trace_summary.py $O/prof_fused/run_kernel_trace.csv $O/prof_split/run_kernel_trace.csv
 for r in 1 2 3; do
-  IRGAN_HEAD_FWD_FUSED=1 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_fused_$r.json 2>/dev/null || { echo "fused $r failed"; exit 1; }
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_split_$r.json 2>/dev/null || { echo "split $r failed"; exit 1; }
+  IRGAN_HEAD_FWD_FUSED=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_fused_$r.json 2>/dev/null || { echo "fused $r failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_split_$r.json 2>/dev/null || { echo "split $r failed"; exit 1; }
 done
 python - <<PY
 import json
