@@ -247,6 +247,57 @@ IRGAN_API int irgan_in_bwd_apply_fp8(const void* dy, int32_t lddy, int32_t dyoff
 IRGAN_API int irgan_channel_sum(const void* g, int32_t dtype, int32_t P, int32_t C, int32_t ld,
                       int32_t off, float* db, double* work, irgan_stream_t s);
 
+/* ---- BatchNorm2d (ir:158-159), single device: affine, running statistics ---- */
+/* Statistics are per channel over GROUPS of consecutive samples of an NHWC slice: G groups
+ * of N / G samples each (N % G == 0; G = 1 is nn.BatchNorm2d over the batch, G = 2 the
+ * [real; fake] batch of the fused step, whose halves the reference normalises in two calls).
+ * Tables stay per (n, c), every sample of a group holding its group's entry:
+ *   mr[n][c] = {mean, rstd, mean_lo, 0} (4 floats; IRGAN_BN_TABLE), rstd = 1 / sqrt(biased var
+ *   + eps), mean + mean_lo the fp64 mean as a two-float sum: xhat = ((x - mean) - mean_lo) * rstd
+ *   keeps its accuracy when |mean| is large against the deviation;
+ *   ab[n][c] = {beta - mean * gamma * rstd, gamma * rstd}: the {shift, scale} form the fused
+ *   resample consumers read with IRGAN_NORM_AFFINE (no division by gamma: gamma == 0 is exact).
+ * Partials are summed in fp64 in a fixed order (no atomics).  With running_mean / running_var
+ * non-NULL they are updated in place, group after group in group order, each group `repeat`
+ * (>= 1) times: r = (1 - momentum) * r + momentum * s, s the group's mean / UNBIASED variance
+ * (x n / (n - 1), n = N / G * HW).  NULL running buffers: no update. */
+enum { IRGAN_BN_TABLE = 4 };        /* floats per (n, c) of mr */
+enum { IRGAN_NORM_AFFINE = 256 };   /* OR-ed into act of irgan_sep_resample_in / _fp8: mr is an ab table */
+/* The finalize half, from the nb float2 {sum, sum of squares} partials per (n, c) that
+ * irgan_conv_fwd_stats wrote.  ab may be NULL. */
+IRGAN_API int irgan_bn_finalize(const void* part, int32_t N, int32_t HW, int32_t C, int32_t nb, int32_t G,
+                      const float* gamma, const float* beta, float* running_mean, float* running_var,
+                      float momentum, float eps, int32_t repeat, float* mr, float* ab, irgan_stream_t s);
+/* Statistics pass over x + finalize.  The pass accumulates {sum x, sum x^2} in fp64 from the
+ * first add on, so a mean that is large against the deviation does not cancel the variance away.
+ * work: IRGAN_IN_PARTS*N*C doubles of scratch. */
+IRGAN_API int irgan_bn_stats(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ld,
+                   int32_t off, int32_t G, const float* gamma, const float* beta, float* running_mean,
+                   float* running_var, float momentum, float eps, int32_t repeat, double* work, float* mr,
+                   float* ab, irgan_stream_t s);
+/* Eval mode: the mr / ab tables of N samples from the running statistics (nothing is updated). */
+IRGAN_API int irgan_bn_eval_table(const float* running_mean, const float* running_var, const float* gamma,
+                        const float* beta, int32_t N, int32_t C, float eps, float* mr, float* ab,
+                        irgan_stream_t s);
+/* y = act(gamma * (x - mean) * rstd + beta) [+ res], act NONE / RELU / LRELU; bf16 or fp32
+ * (x, res, y of one dtype); 8-channel vectors, scalar when C or a stride / offset % 8 != 0. */
+IRGAN_API int irgan_bn_apply(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ldx,
+                   int32_t xoff, const float* mr, const float* gamma, const float* beta, int32_t act,
+                   const void* res, int32_t ldr, int32_t roff, void* y, int32_t ldy, int32_t yoff,
+                   irgan_stream_t s);
+/* Backward of irgan_bn_apply given the PRE-norm x: xhat = (x - mean) * rstd,
+ * g = (dy [+ dy2]) * act'(gamma * xhat + beta) (the mask on the AFFINE output),
+ * dx = gamma * rstd * (g - mean g - xhat * mean(g * xhat)), the means per (group, channel) in
+ * fp64 in a fixed order; dbeta[c] += sum g, dgamma[c] += sum g * xhat over ALL groups (fp32,
+ * one add per channel, no atomics).  eval != 0: mr holds the running statistics and
+ * dx = gamma * rstd * g.  dx may alias dy.  work: IRGAN_IN_PARTS*N*C doubles, red: 2*N*C floats. */
+IRGAN_API int irgan_bn_backward(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff, const void* dy2,
+                      int32_t dy2_dtype, int32_t lddy2, int32_t dy2off, const void* x, int32_t x_dtype,
+                      int32_t ldx, int32_t xoff, int32_t act, int32_t N, int32_t HW, int32_t C, int32_t G,
+                      int32_t eval, const float* mr, const float* gamma, const float* beta, double* work,
+                      float* red, void* dx, int32_t dx_dtype, int32_t lddx, int32_t dxoff, float* dgamma,
+                      float* dbeta, irgan_stream_t s);
+
 /* ---- resampling (ir:269-355 and reflection-pad backward) ---- */
 /* Per-axis tables of a separable resampling map (host only, no GPU work).
  * kind 0: Downsample = reflect pad 1 + [1,2,1]/4 taps, stride 2 (ir:269-310);

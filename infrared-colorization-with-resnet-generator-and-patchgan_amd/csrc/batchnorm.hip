@@ -1,0 +1,490 @@
+// BatchNorm2d forward / backward (NHWC), single device: nn.BatchNorm2d of ir:158-159
+// (eps 1e-5, momentum 0.1, affine, running statistics) + the fused ReLU / LeakyReLU(0.2) /
+// residual add, and their autograd backward.
+//
+// Statistics are per channel over a GROUP of consecutive samples (G groups of N / G samples,
+// include/irgan.h).  Same structure as norm.hip: HBM-bound row passes in which a thread owns 8
+// consecutive channels (16-byte bf16 / 2 x 16-byte fp32 loads; a scalar form for C % 8 != 0 or
+// unaligned slices), one partial pair per (block, channel), and a finalize launch that sums
+// the partials of a group in fp64 in a fixed order -- no atomics anywhere, the gamma / beta
+// gradients included.  The tables stay per (n, c) (each sample carries its group's entry), so
+// the apply / backward passes and the fused resample consumers index them as InstanceNorm's;
+// the statistics table holds {mean, rstd, mean_lo, 0} (the mean as a two-float sum).
+#include "common.h"
+
+#include <algorithm>
+#include <initializer_list>
+
+namespace {
+
+constexpr int TPB = 256;
+constexpr int V = 8;
+constexpr int BN_PARTS = 128;   // row-pass blocks per image: 128 double2 partials fill the work size
+static_assert(2 * BN_PARTS <= IRGAN_IN_PARTS, "work buffer: IRGAN_IN_PARTS doubles per (n, c)");
+
+template <int VW>
+IRGAN_HD void ldw(const void* p, int dt, long i, float* o) {
+    if constexpr (VW == 8) {
+        if (dt == IRGAN_BF16) {
+            const uint4 u = *(const uint4*)((const bf16_t*)p + i);
+            const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                o[2 * k] = __uint_as_float(w[k] << 16);
+                o[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
+            }
+        } else {
+            const float4 a = *(const float4*)((const float*)p + i), b = *(const float4*)((const float*)p + i + 4);
+            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+        }
+    } else {
+        o[0] = ldv(p, dt, i);
+    }
+}
+template <int VW>
+IRGAN_HD void stw(void* p, int dt, long i, const float* v) {
+    if constexpr (VW == 8) {
+        if (dt == IRGAN_BF16) {
+            uint4 u;
+            u.x = pk_bf16(v[0], v[1]);
+            u.y = pk_bf16(v[2], v[3]);
+            u.z = pk_bf16(v[4], v[5]);
+            u.w = pk_bf16(v[6], v[7]);
+            *(uint4*)((bf16_t*)p + i) = u;
+        } else {
+            *(float4*)((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4*)((float*)p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+    } else {
+        stv(p, dt, i, v[0]);
+    }
+}
+
+// the affine output gamma * xhat + beta: ONE expression for the forward and for the backward's
+// activation mask, so both see the same sign
+IRGAN_HD float bn_affine(float xh, float g, float b) { return fmaf(g, xh, b); }
+// xhat from the table entry {mean, rstd, mean_lo}: the mean as a two-float sum, so that its
+// fp32 rounding (half an ulp of |mean|) does not reach xhat when |mean| >> the deviation
+IRGAN_HD float bn_xhat(float x, float mean, float mlo, float rstd) { return ((x - mean) - mlo) * rstd; }
+IRGAN_HD float bn_act(float h, int act) {
+    if (act == IRGAN_ACT_RELU) return h > 0.f ? h : 0.f;
+    if (act == IRGAN_ACT_LRELU) return h > 0.f ? h : 0.2f * h;
+    return h;
+}
+IRGAN_HD float bn_act_grad(float h, int act) {
+    if (act == IRGAN_ACT_RELU) return h > 0.f ? 1.f : 0.f;
+    if (act == IRGAN_ACT_LRELU) return h > 0.f ? 1.f : 0.2f;
+    return 1.f;
+}
+
+struct Slice {
+    const void* p;
+    int dt, ld, off;
+};
+
+// Forward statistics: double2 partials {sum x, sum x^2} per (block, channel), accumulated in
+// fp64 from the first add on (the products of two floats are exact in fp64), so neither a mean
+// that is large against the deviation nor a long sum costs accuracy; the pass stays HBM-bound
+// (three fp64 operations per loaded element).  Block layout as bn_rows_kernel.
+template <int VW>
+__global__ __launch_bounds__(TPB) void bn_stats_kernel(Slice X, int HW, int C, int rows_per_block,
+                                                       double2* __restrict__ part) {
+    __shared__ double s0[TPB * VW], s1[TPB * VW];
+    const int n = blockIdx.y;
+    const int r0 = blockIdx.x * rows_per_block;
+    const int r1 = min(HW, r0 + rows_per_block);
+    int CL = (C + VW - 1) / VW;
+    if (CL > TPB) CL = TPB;
+    const int RP = TPB / CL, cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    for (int cb = 0; cb < C; cb += CL * VW) {
+        const int c = cb + cl * VW;
+        const bool on = rl < RP && c < C;   // VW == 8 only with C % 8 == 0: c + 8 <= C
+        double a0[VW], a1[VW];
+#pragma unroll
+        for (int k = 0; k < VW; ++k) { a0[k] = 0.0; a1[k] = 0.0; }
+        if (on) {
+#pragma unroll 4
+            for (int r = r0 + rl; r < r1; r += RP) {
+                float xv[VW];
+                ldw<VW>(X.p, X.dt, ((long)n * HW + r) * X.ld + X.off + c, xv);
+#pragma unroll
+                for (int k = 0; k < VW; ++k) {
+                    const double d = (double)xv[k];
+                    a0[k] += d;
+                    a1[k] = fma(d, d, a1[k]);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < VW; ++k) {
+            s0[threadIdx.x * VW + k] = a0[k];
+            s1[threadIdx.x * VW + k] = a1[k];
+        }
+        __syncthreads();
+        if (on && rl == 0) {   // the first row of lanes sums the RP rows in order
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
+                double t0 = 0.0, t1 = 0.0;
+                for (int j = 0; j < RP; ++j) {
+                    t0 += s0[(j * CL + cl) * VW + k];
+                    t1 += s1[(j * CL + cl) * VW + k];
+                }
+                part[((long)n * gridDim.x + blockIdx.x) * C + c + k] = make_double2(t0, t1);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// MODE 1: float2 partials {sum g, sum g * xhat}; MODE 2: dx (no partials).
+// Block: CL lanes across the channels (VW each), RP rows in parallel; grid (blocks per image, N).
+template <int MODE, int VW>
+__global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice DY2, int act,
+                                                      const float* __restrict__ mr, const float* __restrict__ red,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      void* dx, int dxdt, int lddx, int dxoff, int HW, int C,
+                                                      int rows_per_block, float2* __restrict__ part) {
+    __shared__ float s0[TPB * VW], s1[TPB * VW];
+    const int n = blockIdx.y;
+    const int r0 = blockIdx.x * rows_per_block;
+    const int r1 = min(HW, r0 + rows_per_block);
+    int CL = (C + VW - 1) / VW;
+    if (CL > TPB) CL = TPB;
+    const int RP = TPB / CL, cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    for (int cb = 0; cb < C; cb += CL * VW) {
+        const int c = cb + cl * VW;
+        const bool on = rl < RP && c < C;   // VW == 8 only with C % 8 == 0: c + 8 <= C
+        float a0[VW], a1[VW], mean[VW], mlo[VW], rstd[VW], ga[VW], be[VW], mg[VW], mgx[VW];
+#pragma unroll
+        for (int k = 0; k < VW; ++k) { a0[k] = 0.f; a1[k] = 0.f; }
+        if (on) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
+                const float4 st = ((const float4*)mr)[(long)n * C + c + k];
+                mean[k] = st.x; rstd[k] = st.y; mlo[k] = st.z; ga[k] = gamma[c + k]; be[k] = beta[c + k];
+                if (MODE == 2) {
+                    const float2 rd = ((const float2*)red)[(long)n * C + c + k];
+                    mg[k] = rd.x; mgx[k] = rd.y;
+                }
+            }
+#pragma unroll 4
+            for (int r = r0 + rl; r < r1; r += RP) {
+                const long p = (long)n * HW + r;
+                float xv[VW];
+                ldw<VW>(X.p, X.dt, p * X.ld + X.off + c, xv);
+                float gv[VW], g2[VW], o[VW];
+                ldw<VW>(DY.p, DY.dt, p * DY.ld + DY.off + c, gv);
+                if (DY2.p) {
+                    ldw<VW>(DY2.p, DY2.dt, p * DY2.ld + DY2.off + c, g2);
+#pragma unroll
+                    for (int k = 0; k < VW; ++k) gv[k] += g2[k];
+                }
+#pragma unroll
+                for (int k = 0; k < VW; ++k) {
+                    const float xh = bn_xhat(xv[k], mean[k], mlo[k], rstd[k]);
+                    const float g = gv[k] * bn_act_grad(bn_affine(xh, ga[k], be[k]), act);
+                    if (MODE == 1) { a0[k] += g; a1[k] += g * xh; }
+                    else o[k] = ga[k] * rstd[k] * (g - mg[k] - xh * mgx[k]);
+                }
+                if (MODE == 2) stw<VW>(dx, dxdt, p * lddx + dxoff + c, o);
+            }
+        }
+        if (MODE == 2) continue;   // uniform across the block
+#pragma unroll
+        for (int k = 0; k < VW; ++k) {
+            s0[threadIdx.x * VW + k] = a0[k];
+            s1[threadIdx.x * VW + k] = a1[k];
+        }
+        __syncthreads();
+        if (on && rl == 0) {   // the first row of lanes sums the RP rows in order
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
+                float t0 = 0.f, t1 = 0.f;
+                for (int j = 0; j < RP; ++j) {
+                    t0 += s0[(j * CL + cl) * VW + k];
+                    t1 += s1[(j * CL + cl) * VW + k];
+                }
+                part[((long)n * gridDim.x + blockIdx.x) * C + c + k] = make_float2(t0, t1);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// fp64 sums of the NG * nb partials of each (group, channel): block = FC channels x FS partial
+// lanes, a lane adds partials sub, sub + FS, ..., then lane 0 of the channel adds the FS lanes
+// in order.  The groups run one after the other (the running buffers take them in order).
+constexpr int FC = 8, FS = 32;
+
+template <typename P2>
+IRGAN_HD void group_sums(const P2* __restrict__ part, int grp, int cnt, int C, int c, int sub, int cl,
+                         double (*s0)[FC], double (*s1)[FC], double& s, double& q) {
+    s = 0.0;
+    q = 0.0;
+    if (c < C) {
+        const P2* p = part + (long)grp * cnt * C + c;   // images grp*NG .. of nb partials each: contiguous
+        for (int j = sub; j < cnt; j += FS) {
+            const P2 v = p[(long)j * C];
+            s += v.x;
+            q += v.y;
+        }
+    }
+    __syncthreads();   // the previous group's reads of s0 / s1
+    s0[sub][cl] = s;
+    s1[sub][cl] = q;
+    __syncthreads();
+    if (sub == 0) {
+        s = 0.0;
+        q = 0.0;
+        for (int k = 0; k < FS; ++k) {
+            s += s0[k][cl];
+            q += s1[k][cl];
+        }
+    }
+}
+
+// forward statistics from {sum x, sum x^2} partials: P2 = double2 (bn_stats_kernel) or float2
+// (irgan_conv_fwd_stats)
+template <typename P2>
+__global__ __launch_bounds__(FC * FS) void bn_finalize_kernel(const P2* __restrict__ part, int N, int C,
+                                                              int nb, int HW, int G, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float* rmean, float* rvar,
+                                                              float momentum, float eps, int repeat,
+                                                              float* __restrict__ mr, float* __restrict__ ab) {
+    __shared__ double s0[FS][FC], s1[FS][FC];
+    const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
+    const int NG = N / G;
+    const bool own = sub == 0 && c < C;
+    float rm = 0.f, rv = 0.f;
+    if (own && rmean) { rm = rmean[c]; rv = rvar[c]; }
+    for (int grp = 0; grp < G; ++grp) {
+        double s, q;
+        group_sums(part, grp, NG * nb, C, c, sub, cl, s0, s1, s, q);
+        if (!own) continue;
+        const double cnt = (double)NG * HW;
+        const double mean = s / cnt;
+        double var = q / cnt - mean * mean;
+        if (var < 0) var = 0;
+        const double rstd = 1.0 / sqrt(var + (double)eps);
+        const float meanf = (float)mean, rstdf = (float)rstd, mlof = (float)(mean - (double)meanf);
+        float a = 0.f, b = 0.f;
+        if (ab) {   // y = x * a + b, from the ROUNDED table the apply pass uses
+            a = gamma[c] * rstdf;
+            b = (float)((double)beta[c] - mean * (double)a);
+        }
+        for (int i = 0; i < NG; ++i) {
+            const long e = (long)(grp * NG + i) * C + c;
+            ((float4*)mr)[e] = make_float4(meanf, rstdf, mlof, 0.f);
+            if (ab) ((float2*)ab)[e] = make_float2(b, a);
+        }
+        if (rmean) {
+            const float unb = (float)(cnt > 1.0 ? var * cnt / (cnt - 1.0) : var);
+            for (int r = 0; r < repeat; ++r) {   // as nn.BatchNorm2d: fp32 buffers, one update per forward
+                rm = (1.f - momentum) * rm + momentum * meanf;
+                rv = (1.f - momentum) * rv + momentum * unb;
+            }
+        }
+    }
+    if (own && rmean) { rmean[c] = rm; rvar[c] = rv; }
+}
+
+// backward means: red[n][c] = the group's {mean g, mean g * xhat} (zeros in eval mode, where the
+// statistics do not depend on x); dbeta / dgamma += the sums over all groups
+__global__ __launch_bounds__(FC * FS) void bn_bwd_finalize_kernel(const float2* __restrict__ part, int N, int C, int nb,
+                                                                  int HW, int G, int eval, float* __restrict__ red,
+                                                                  float* __restrict__ dgamma,
+                                                                  float* __restrict__ dbeta) {
+    __shared__ double s0[FS][FC], s1[FS][FC];
+    const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
+    const int NG = N / G;
+    const bool own = sub == 0 && c < C;
+    double ts = 0.0, tq = 0.0;
+    for (int grp = 0; grp < G; ++grp) {
+        double s, q;
+        group_sums(part, grp, NG * nb, C, c, sub, cl, s0, s1, s, q);
+        if (!own) continue;
+        ts += s;
+        tq += q;
+        const double cnt = (double)NG * HW;
+        const float m0 = eval ? 0.f : (float)(s / cnt), m1 = eval ? 0.f : (float)(q / cnt);
+        for (int i = 0; i < NG; ++i) {
+            const long e = 2 * ((long)(grp * NG + i) * C + c);
+            red[e] = m0;
+            red[e + 1] = m1;
+        }
+    }
+    if (own) {
+        if (dbeta) dbeta[c] += (float)ts;
+        if (dgamma) dgamma[c] += (float)tq;
+    }
+}
+
+__global__ __launch_bounds__(TPB) void bn_eval_table_kernel(const float* __restrict__ rmean, const float* __restrict__ rvar,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            int N, int C, float eps, float* __restrict__ mr,
+                                                            float* __restrict__ ab) {
+    const int c = blockIdx.x * TPB + threadIdx.x;
+    if (c >= C) return;
+    const float mean = rmean[c];
+    const float rstd = (float)(1.0 / sqrt((double)rvar[c] + (double)eps));
+    const float a = gamma[c] * rstd;
+    const float b = (float)((double)beta[c] - (double)mean * (double)a);
+    for (int n = 0; n < N; ++n) {
+        const long e = (long)n * C + c;
+        ((float4*)mr)[e] = make_float4(mean, rstd, 0.f, 0.f);
+        if (ab) ((float2*)ab)[e] = make_float2(b, a);
+    }
+}
+
+template <int VW>
+__global__ __launch_bounds__(TPB) void bn_apply_kernel(Slice X, int HW, int C, const float* __restrict__ mr,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                       int act, Slice R, void* __restrict__ y, int ldy, int yoff,
+                                                       long total) {
+    const int CV = C / VW;
+    for (long idx = blockIdx.x * (long)TPB + threadIdx.x; idx < total; idx += (long)gridDim.x * TPB) {
+        const long p = idx / CV;
+        const int c = (int)(idx - p * CV) * VW;
+        const int n = (int)(p / HW);
+        float v[VW];
+        ldw<VW>(X.p, X.dt, p * X.ld + X.off + c, v);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) {
+            const float4 st = ((const float4*)mr)[(long)n * C + c + k];
+            v[k] = bn_act(bn_affine(bn_xhat(v[k], st.x, st.z, st.y), gamma[c + k], beta[c + k]), act);
+        }
+        if (R.p) {
+            float rv[VW];
+            ldw<VW>(R.p, R.dt, p * R.ld + R.off + c, rv);
+#pragma unroll
+            for (int k = 0; k < VW; ++k) v[k] += rv[k];
+        }
+        stw<VW>(y, X.dt, p * ldy + yoff + c, v);
+    }
+}
+
+bool vec_ok(int C, std::initializer_list<int> lds) {
+    if (C % V) return false;
+    for (int l : lds)
+        if (l % V) return false;
+    return true;
+}
+
+// grid of a row pass: >= 8 rows per thread, ~4096 blocks in all, <= BN_PARTS per image
+void rows_grid(int N, int HW, int C, bool vec, int* nb, int* rows) {
+    int cl = vec ? C / V : C;
+    if (cl > TPB) cl = TPB;
+    const int RP = TPB / cl;
+    long b = std::min<long>((4096 + N - 1) / N, irgan_cdiv(HW, 8L * RP));
+    b = std::max<long>(1, std::min<long>(b, BN_PARTS));
+    *rows = irgan_cdiv(HW, b);
+    *nb = irgan_cdiv(HW, *rows);
+}
+
+bool dt_ok(int dt) { return dt == IRGAN_F32 || dt == IRGAN_BF16; }
+
+}  // namespace
+
+extern "C" int irgan_bn_finalize(const void* part, int32_t N, int32_t HW, int32_t C, int32_t nb, int32_t G,
+                                 const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                 float momentum, float eps, int32_t repeat, float* mr, float* ab, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!part || !mr || nb < 1 || nb > IRGAN_IN_PARTS || G < 1 || N % G || repeat < 1 || (ab && (!gamma || !beta)) ||
+        (!running_mean != !running_var))
+        return IRGAN_EINVAL;
+    bn_finalize_kernel<float2><<<irgan_cdiv(C, FC), FC * FS, 0, (hipStream_t)s>>>(
+        (const float2*)part, N, C, nb, HW, G, gamma, beta, running_mean, running_var, momentum, eps, repeat, mr, ab);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_stats(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ld, int32_t off,
+                              int32_t G, const float* gamma, const float* beta, float* running_mean,
+                              float* running_var, float momentum, float eps, int32_t repeat, double* work, float* mr,
+                              float* ab, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!x || !work || !mr || !dt_ok(dtype) || G < 1 || N % G || repeat < 1 || (ab && (!gamma || !beta)) ||
+        (!running_mean != !running_var) || off < 0 || off + C > ld)
+        return IRGAN_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    const bool vec = vec_ok(C, {ld, off});
+    int nb, rows;
+    rows_grid(N, HW, C, vec, &nb, &rows);
+    const Slice X{x, dtype, ld, off};
+    const dim3 g(nb, N);   // nb <= BN_PARTS double2 partials per (n, c): 2 * 128 doubles of the work buffer's 256
+    if (vec)
+        bn_stats_kernel<V><<<g, TPB, 0, st>>>(X, HW, C, rows, (double2*)work);
+    else
+        bn_stats_kernel<1><<<g, TPB, 0, st>>>(X, HW, C, rows, (double2*)work);
+    bn_finalize_kernel<double2><<<irgan_cdiv(C, FC), FC * FS, 0, st>>>(
+        (const double2*)work, N, C, nb, HW, G, gamma, beta, running_mean, running_var, momentum, eps, repeat, mr, ab);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_eval_table(const float* running_mean, const float* running_var, const float* gamma,
+                                   const float* beta, int32_t N, int32_t C, float eps, float* mr, float* ab,
+                                   irgan_stream_t s) {
+    if ((long)N * C <= 0) return 0;
+    if (!running_mean || !running_var || !gamma || !beta || !mr) return IRGAN_EINVAL;
+    bn_eval_table_kernel<<<irgan_cdiv(C, TPB), TPB, 0, (hipStream_t)s>>>(running_mean, running_var, gamma, beta, N, C, eps,
+                                                                        mr, ab);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_apply(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ldx, int32_t xoff,
+                              const float* mr, const float* gamma, const float* beta, int32_t act, const void* res,
+                              int32_t ldr, int32_t roff, void* y, int32_t ldy, int32_t yoff, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!x || !mr || !gamma || !beta || !y || !dt_ok(dtype) || act < IRGAN_ACT_NONE || act > IRGAN_ACT_LRELU ||
+        xoff < 0 || xoff + C > ldx || yoff < 0 || yoff + C > ldy || (res && (roff < 0 || roff + C > ldr)))
+        return IRGAN_EINVAL;
+    const bool vec = vec_ok(C, {ldx, xoff, ldy, yoff}) && (!res || vec_ok(C, {ldr, roff}));
+    const int VW = vec ? V : 1;
+    const long total = (long)N * HW * (C / VW);
+    const int blocks = (int)std::min<long>((total + TPB - 1) / TPB, 16384);
+    const Slice X{x, dtype, ldx, xoff}, R{res, dtype, ldr, roff};
+    if (vec)
+        bn_apply_kernel<V><<<blocks, TPB, 0, (hipStream_t)s>>>(X, HW, C, mr, gamma, beta, act, R, y, ldy, yoff, total);
+    else
+        bn_apply_kernel<1><<<blocks, TPB, 0, (hipStream_t)s>>>(X, HW, C, mr, gamma, beta, act, R, y, ldy, yoff, total);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_backward(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff, const void* dy2,
+                                 int32_t dy2_dtype, int32_t lddy2, int32_t dy2off, const void* x, int32_t x_dtype,
+                                 int32_t ldx, int32_t xoff, int32_t act, int32_t N, int32_t HW, int32_t C, int32_t G,
+                                 int32_t eval, const float* mr, const float* gamma, const float* beta, double* work,
+                                 float* red, void* dx, int32_t dx_dtype, int32_t lddx, int32_t dxoff, float* dgamma,
+                                 float* dbeta, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!dy || !x || !mr || !gamma || !beta || !work || !red || !dx || !dt_ok(dy_dtype) || !dt_ok(x_dtype) ||
+        !dt_ok(dx_dtype) || (dy2 && !dt_ok(dy2_dtype)) || G < 1 || N % G || act < IRGAN_ACT_NONE ||
+        act > IRGAN_ACT_LRELU || dyoff < 0 || dyoff + C > lddy || xoff < 0 || xoff + C > ldx || dxoff < 0 ||
+        dxoff + C > lddx || (dy2 && (dy2off < 0 || dy2off + C > lddy2)))
+        return IRGAN_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff, lddx, dxoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
+    int nb, rows;
+    rows_grid(N, HW, C, vec, &nb, &rows);
+    const Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
+    const dim3 g(nb, N);
+    if (vec)
+        bn_rows_kernel<1, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, nullptr, gamma, beta, nullptr, 0, 0, 0, HW, C,
+                                                rows, (float2*)work);
+    else
+        bn_rows_kernel<1, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, nullptr, gamma, beta, nullptr, 0, 0, 0, HW, C,
+                                                rows, (float2*)work);
+    bn_bwd_finalize_kernel<<<irgan_cdiv(C, FC), FC * FS, 0, st>>>((const float2*)work, N, C, nb, HW, G, eval, red, dgamma,
+                                                                  dbeta);
+    if (vec)
+        bn_rows_kernel<2, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, red, gamma, beta, dx, dx_dtype, lddx, dxoff, HW, C,
+                                                rows, nullptr);
+    else
+        bn_rows_kernel<2, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, red, gamma, beta, dx, dx_dtype, lddx, dxoff, HW, C,
+                                                rows, nullptr);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}

@@ -146,11 +146,14 @@ __global__ __launch_bounds__(NT) void sep_lds_kernel(const void* __restrict__ in
     const int G = CB >> 3;  // 8-channel groups
     float nm[NORM ? 8 : 1], nr[NORM ? 8 : 1];
     if constexpr (NORM) {
+        // IRGAN_NORM_AFFINE: the table holds {shift, scale} itself (BatchNorm's gamma / beta folded in)
+        const bool aff = (act & IRGAN_NORM_AFFINE) != 0;
+        act &= 0xff;
         const float4* m4 = (const float4*)(mr + 2 * ((long)n * C + c0 + (threadIdx.x % G) * 8));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float4 t = m4[k];
-            nm[2 * k] = -t.x * t.y; nr[2 * k] = t.y; nm[2 * k + 1] = -t.z * t.w; nr[2 * k + 1] = t.w;
+            nm[2 * k] = aff ? t.x : -t.x * t.y; nr[2 * k] = t.y; nm[2 * k + 1] = aff ? t.z : -t.z * t.w; nr[2 * k + 1] = t.w;
         }  // nm = -mean * rstd: (z - mean) * rstd as one FMA per loaded element
     }
     float wyv[TM];
@@ -293,11 +296,13 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
     }
     float nm[NORM ? 8 : 1], nr[NORM ? 8 : 1];
     if constexpr (NORM) {
+        const bool aff = (act & IRGAN_NORM_AFFINE) != 0;   // {shift, scale} table (sep_lds_kernel)
+        act &= 0xff;
         const float4* m4 = (const float4*)(mr + 2 * ((long)n * C + c0 + (tid % G) * 8));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float4 t = m4[k];
-            nm[2 * k] = -t.x * t.y; nr[2 * k] = t.y; nm[2 * k + 1] = -t.z * t.w; nr[2 * k + 1] = t.w;
+            nm[2 * k] = aff ? t.x : -t.x * t.y; nr[2 * k] = t.y; nm[2 * k + 1] = aff ? t.z : -t.z * t.w; nr[2 * k + 1] = t.w;
         }
     }
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(

@@ -37,16 +37,22 @@ IMAGENET_STD = (0.229, 0.224, 0.225)    # ir:673
 # ----------------------------------------------------------------------------
 
 def g_param_shapes(input_nc=1, output_nc=3, ngf=64, n_blocks=9, no_antialias=False, no_antialias_up=False,
-                   use_bias=True, padding_type="reflect", use_dropout=False):
+                   use_bias=True, padding_type="reflect", use_dropout=False, batch_norm=False):
     """ResnetUNetGenerator state_dict layout (ir:443-531), buffers included.  use_bias:
     the reference's ``norm_layer == nn.InstanceNorm2d`` (ir:450-455); without it (norm
-    'none') every conv but outc, and the ConvTranspose2d, has no bias."""
+    'none' / 'batch') every conv but outc, and the ConvTranspose2d, has no bias.
+    batch_norm: nn.BatchNorm2d's entries (bn_param_shapes) at the module index after each
+    normalised conv."""
     s = OrderedDict()
+    use_bias = use_bias and not batch_norm
 
-    def conv(key, shape):
+    def conv(key, shape, normed=True):
         s[key + ".weight"] = shape
         if use_bias:
             s[key + ".bias"] = (shape[0],)
+        if batch_norm and normed:
+            seq, idx = key.rsplit(".", 1)
+            s.update(bn_param_shapes(f"{seq}.{int(idx) + 1}", shape[0]))
     conv("inc.1", (ngf, input_nc, 7, 7))
     conv("down1.0", (2 * ngf, ngf, 3, 3))
     if not no_antialias:
@@ -59,12 +65,21 @@ def g_param_shapes(input_nc=1, output_nc=3, ngf=64, n_blocks=9, no_antialias=Fal
             conv(f"resblocks.{b}.conv_block.{c}", (4 * ngf, 4 * ngf, 3, 3))
     for name, ch, cat in (("up1", 4 * ngf, 6 * ngf), ("up2", 2 * ngf, 3 * ngf)):
         if no_antialias_up:
-            conv(f"{name}_up", (ch, ch, 3, 3))
+            conv(f"{name}_up", (ch, ch, 3, 3), normed=False)
         else:
             s[f"{name}_up.filt"] = (ch, 1, 3, 3)
         conv(f"{name}_conv.0", (ch // 2, cat, 3, 3))
     s["outc.1.weight"] = (output_nc, ngf, 7, 7); s["outc.1.bias"] = (output_nc,)
     return s
+
+
+def bn_param_shapes(key, C):
+    """nn.BatchNorm2d's state_dict entries under module ``key``, in its order."""
+    return OrderedDict([(key + ".weight", (C,)), (key + ".bias", (C,)), (key + ".running_mean", (C,)),
+                        (key + ".running_var", (C,)), (key + ".num_batches_tracked", ())])
+
+
+BN_BUFFERS = (".running_mean", ".running_var", ".num_batches_tracked")
 
 
 def d_layers(n_layers=3):
@@ -86,15 +101,19 @@ def d_channels(input_nc=4, ndf=64, n_layers=3):
     return [input_nc] + [ndf * min(2 ** n, 8) for n in range(n_layers + 1)] + [1]
 
 
-def d_param_shapes(input_nc=4, ndf=64, n_layers=3, use_bias=True):
+def d_param_shapes(input_nc=4, ndf=64, n_layers=3, use_bias=True, batch_norm=False):
     """NLayerDiscriminator layout (ir:585-632); the first and last convs always carry a
-    bias, the normalised ones only with InstanceNorm (use_bias, ir:588-593)."""
+    bias, the normalised ones only with InstanceNorm (use_bias, ir:588-593); batch_norm:
+    nn.BatchNorm2d's entries after each normalised conv."""
     s = OrderedDict()
+    use_bias = use_bias and not batch_norm
     ch = d_channels(input_nc, ndf, n_layers)
     for i, (key, _, normed) in enumerate(d_layers(n_layers)):
         s[key + ".weight"] = (ch[i + 1], ch[i], 4, 4)
         if use_bias or not normed:
             s[key + ".bias"] = (ch[i + 1],)
+        if batch_norm and normed:
+            s.update(bn_param_shapes(f"model.{int(key.split('.')[1]) + 1}", ch[i + 1]))
     return s
 
 
@@ -109,10 +128,23 @@ def vgg_param_shapes():
 
 
 class ParamStore:
-    """Flat fp32 parameter / gradient / Adam-moment buffers for one network."""
+    """Flat fp32 parameter / gradient / Adam-moment buffers for one network.
+
+    BatchNorm's running statistics (``buffers``) are tensors of their own, outside the flat
+    range Adam and the gradient reduce walk: fp32 on the device, num_batches_tracked an int64
+    scalar on the host (momentum is fixed, so no kernel reads it)."""
 
     def __init__(self, shapes: "OrderedDict[str, tuple]", device, with_grad=True, with_adam=True):
-        self.shapes = OrderedDict((k, tuple(v)) for k, v in shapes.items() if not k.endswith(".filt"))
+        self.layout = [k for k in shapes if not k.endswith(".filt")]   # state order, buffers included
+        self.buffers = OrderedDict()
+        for k in self.layout:
+            if k.endswith(".running_mean"):
+                self.buffers[k] = torch.zeros(shapes[k], device=device)
+            elif k.endswith(".running_var"):
+                self.buffers[k] = torch.ones(shapes[k], device=device)
+            elif k.endswith(".num_batches_tracked"):
+                self.buffers[k] = torch.zeros((), dtype=torch.int64)
+        self.shapes = OrderedDict((k, tuple(shapes[k])) for k in self.layout if k not in self.buffers)
         self.offsets, off = {}, 0
         for k, shp in self.shapes.items():
             self.offsets[k] = off
@@ -147,21 +179,25 @@ class ParamStore:
     def load(self, state: dict, strict=False):
         """Copy OIHW tensors (reference checkpoint / state_dict) into the store."""
         missing = []
-        for k in self.shapes:
+        for k in self.layout:
             if k not in state:
                 missing.append(k)
                 continue
             src = state[k]
-            dst = self.oihw(k)
+            dst = self.buffers[k] if k in self.buffers else self.oihw(k)
             if tuple(src.shape) != tuple(dst.shape):
                 raise RuntimeError(f"size mismatch for {k}: copying {tuple(src.shape)} into {tuple(dst.shape)}")
-            dst.copy_(src.to(self.device, torch.float32))
+            dst.copy_(src.to(dst.device, dst.dtype))
         if strict and missing:
             raise RuntimeError(f"missing keys {missing}")
         return missing
 
     def state(self, buf=None):
-        return OrderedDict((k, self.oihw(k, buf)) for k in self.shapes)
+        """Parameters (of ``buf``, default the weights) and, for the weights, BatchNorm's buffers,
+        in state_dict order."""
+        if buf is not None:
+            return OrderedDict((k, self.oihw(k, buf)) for k in self.shapes)
+        return OrderedDict((k, self.buffers[k] if k in self.buffers else self.oihw(k)) for k in self.layout)
 
     def zero_grad(self):
         self.grad.zero_()
@@ -352,9 +388,11 @@ class INLayer:
         if q8 is not None:
             ops.fp8_quant(y, *q8)
 
-    def bwd(self, bufs: Buffers, name: str, dy: Feat, z: Feat, act, dx: Feat, db=None, dy2: Feat = None, q8=None):
+    def bwd(self, bufs: Buffers, name: str, dy: Feat, z: Feat, act, dx: Feat, db=None, dy2: Feat = None, q8=None,
+            wgrad=True):
         """z: the PRE-norm input kept from forward; act: the activation after IN.
-        q8: also write dx's fp8 copy (ops.in_backward)."""
+        q8: also write dx's fp8 copy (ops.in_backward).  wgrad: accumulate the norm's own
+        parameter gradients (BNLayer; InstanceNorm has none)."""
         N, C = z.N, z.C
         work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
         red = bufs.flat("in_red", 2 * N * C)
@@ -395,7 +433,7 @@ class NoNorm(INLayer):
         ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
         return self._ident(bufs, name, z.N, z.C)
 
-    def bwd(self, bufs, name, dy, z, act, dx, db=None, dy2=None, q8=None):
+    def bwd(self, bufs, name, dy, z, act, dx, db=None, dy2=None, q8=None, wgrad=True):
         if dy2 is not None or q8 is not None:
             raise NotImplementedError("NoNorm.bwd: dy2 / q8 are InstanceNorm-path features")
         if act == ACT_NONE and dx.t.data_ptr() == dy.t.data_ptr() and dx.off == dy.off:
@@ -405,14 +443,112 @@ class NoNorm(INLayer):
         if db is not None:
             ops.channel_sum(dx, db)
 
-def make_norm(norm: str) -> INLayer:
-    """The engine's per-layer norm for Config.norm (ir:154-165): 'instance' or 'none'
-    ('batch' needs cross-sample statistics (SyncBN under DP): out of scope)."""
+class BNLayer(INLayer):
+    """norm='batch' (ir:158-159: nn.BatchNorm2d, eps 1e-5, momentum 0.1, affine, running
+    statistics) on one device; the conv in front has no bias (ir:450-455, 588-593).  Same
+    interface as INLayer.  gamma / beta (and their gradients) are the layer's slices of the
+    ParamStore flat buffers, so Adam, the optimizer state and the gradient reduce cover them
+    like any conv weight; the running buffers are ``store.buffers`` tensors.
+
+    ``groups``: statistics per group of N / groups consecutive samples (csrc/batchnorm.hip):
+    1 is nn.BatchNorm2d over the batch; the fused step's D forward on [real; fake] runs with 2,
+    which is the reference's netD(real), netD(fake) (ir:1642-1643) -- the running buffers take
+    the groups in that order.  ``repeat``: the running update of one forward applied that many
+    times, for a forward that stands for several identical ones of the reference (the fused step
+    runs G once where ir:1638 and ir:1657 run it twice on the same weights and input).
+    ``training`` False: the running statistics normalise and nothing is updated (model.eval())."""
+
+    def __init__(self, store: "ParamStore", key: str):
+        self.store, self.key = store, key
+        self.gamma, self.beta = store.krsc(key + ".weight"), store.krsc(key + ".bias")
+        self.dgamma = store.krsc(key + ".weight", store.grad) if store.grad is not None else None
+        self.dbeta = store.krsc(key + ".bias", store.grad) if store.grad is not None else None
+        self.running_mean = store.buffers[key + ".running_mean"]
+        self.running_var = store.buffers[key + ".running_var"]
+        self.num_batches_tracked = store.buffers[key + ".num_batches_tracked"]
+        self.training, self.groups, self.repeat = True, 1, 1
+
+    def configure(self, training=True, groups=1, repeat=1):
+        self.training, self.groups, self.repeat = bool(training), int(groups), int(repeat)
+
+    def _tables(self, bufs: Buffers, name: str, x: Feat, nb=0, want_ab=False):
+        """x's {mean, rstd} table (kept for bwd()) and, if asked, the {shift, scale} one."""
+        N, C = x.N, x.C
+        mr = bufs.get("mr_" + name, (N * C * ops.BN_TABLE,), torch.float32)
+        ab = bufs.get("ab_" + name, (N * C * 2,), torch.float32) if want_ab else None
+        bufs.state["bn_" + name] = (self.training, self.groups)
+        if not self.training:
+            ops.bn_eval_table(self.running_mean, self.running_var, self.gamma, self.beta, N, mr, ab)
+            return mr, ab
+        work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
+        ops.bn_stats(x, work, mr, self.groups, self.gamma, self.beta, self.running_mean, self.running_var, self.repeat,
+                     ab=ab, nb=nb)
+        self.num_batches_tracked += self.repeat * self.groups
+        return mr, ab
+
+    def fwd(self, bufs, name, x, y, act, res=None, xhat=None, nb=0, q8=None):
+        if q8 is not None or xhat is not None:
+            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+        mr, _ = self._tables(bufs, name, x, nb)
+        ops.bn_apply(x, mr, self.gamma, self.beta, y, act=act, res=res)
+
+    def conv_fwd8(self, *a, **kw):
+        raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+
+    def _conv(self, bufs, pc, x, z):
+        """z = conv(x); the partials per image in the work buffer (0: none were written)."""
+        nb = 0
+        if self.training and INLayer.fused_stats:
+            nb = ops.conv_fwd_stats(pc, x, z, bufs.flat("in_work", ops.IN_PARTS * z.N * z.C, torch.float64))
+        if not nb:
+            ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
+        return nb
+
+    def conv_fwd(self, bufs, name, pc, x, z, y, act, res=None):
+        self.fwd(bufs, name, z, y, act, res=res, nb=self._conv(bufs, pc, x, z))
+
+    def conv_stats(self, bufs, name, pc, x, z, conv8=None):
+        """z = conv(x); returns the {shift, scale} table the fused resample consumers read with
+        ops.NORM_AFFINE (the {mean, rstd} table stays in ``bufs`` for bwd())."""
+        if conv8 is not None:
+            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+        return self._tables(bufs, name, z, self._conv(bufs, pc, x, z), want_ab=True)[1]
+
+    def resample_fwd(self, bufs, name, pc, x, z, a_name, act, y, fused, plain, conv8=None, q8=None):
+        if q8 is not None:
+            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+        ab = self.conv_stats(bufs, name, pc, x, z, conv8=conv8)
+        if INLayer.fused_resample and fused(z, ab, act | ops.NORM_AFFINE, y):
+            return
+        a = Feat(bufs.get(a_name, (z.N, z.H, z.W, z.C), z.t.dtype))
+        ops.bn_apply(z, bufs.d["mr_" + name], self.gamma, self.beta, a, act=act)
+        plain(a, y)
+
+    def bwd(self, bufs, name, dy, z, act, dx, db=None, dy2=None, q8=None, wgrad=True):
+        if q8 is not None:
+            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+        training, groups = bufs.state["bn_" + name]
+        N, C = z.N, z.C
+        work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
+        red = bufs.flat("in_red", 2 * N * C)
+        ops.bn_backward(dy, z, act, bufs.d["mr_" + name], self.gamma, self.beta, work, red, dx,
+                        dgamma=self.dgamma if wgrad else None, dbeta=self.dbeta if wgrad else None, groups=groups,
+                        eval_mode=not training, dy2=dy2)
+
+
+def make_norm(norm: str, store: "ParamStore" = None, key: str = None) -> INLayer:
+    """The engine's per-layer norm for Config.norm (ir:154-165): 'instance', 'none' or 'batch'.
+    'batch' (BNLayer) takes the layer's ParamStore and the state key of its nn.BatchNorm2d
+    module; it is single-device BatchNorm (statistics over the local batch) -- under a process
+    group of more than one rank the reference semantics would need SyncBN, the one remaining
+    gap (GANTrainer refuses that combination)."""
     if norm == "instance":
         return INLayer()
     if norm in ("none", None):
         return NoNorm()
-    raise NotImplementedError(f"norm '{norm}': the HIP engines implement 'instance' and 'none'")
+    if norm == "batch":
+        return BNLayer(store, key)
+    raise NotImplementedError(f"norm '{norm}': the HIP engines implement 'instance', 'none' and 'batch'")
 
 
 def res_conv_keys(padding_type="reflect", use_dropout=False):
@@ -493,8 +629,12 @@ class GeneratorEngine:
             self.s_cat, self.s_dz3, self.s_dz2 = 4 * n_blocks, 4 * n_blocks + 1, 4 * n_blocks + 2
             self.s_x1 = 4 * n_blocks + 3   # down2's own x1 copy on the calibration step
         n_in = 5 + 2 * n_blocks
-        self.norms = {k: make_norm(norm) for k in ["inc", "down1", "down2", "up1", "up2"] +
-                      [f"r{b}_{i}" for b in range(n_blocks) for i in (1, 2)]}
+        # name -> state key of the layer's norm module (the index after its conv)
+        nkeys = {"inc": "inc.2", "down1": "down1.1", "down2": "down2.1", "up1": "up1_conv.1", "up2": "up2_conv.1"}
+        for b in range(n_blocks):
+            nkeys[f"r{b}_1"] = f"resblocks.{b}.conv_block.{k1 + 1}"
+            nkeys[f"r{b}_2"] = f"resblocks.{b}.conv_block.{k2 + 1}"
+        self.norms = {k: make_norm(norm, S, key) for k, key in nkeys.items()}
         assert len(self.norms) == n_in
         self.bufs = Buffers(store.device)
 
@@ -553,14 +693,19 @@ class GeneratorEngine:
         res = ok(H2, W2, c2)
         return res, res and self.fp8_ud and ok(H1, W1, c2 + c1)
 
-    def forward(self, ir_nchw: torch.Tensor, bufs: Buffers = None, training: bool = None) -> torch.Tensor:
+    def forward(self, ir_nchw: torch.Tensor, bufs: Buffers = None, training: bool = None,
+                bn_repeat: int = 1) -> torch.Tensor:
         """ir (B, input_nc, H, W) fp32 in [-1,1] -> fake NHWC fp32 (B, H, W, 3).
         Activations land in ``bufs`` (default: the engine's own set).  ``training``
-        (default: self.training) decides nn.Dropout's mode (ir:394-395): callers outside
-        the module forward / GANStep pass the module's train()/eval() state."""
+        (default: self.training) decides nn.Dropout's and nn.BatchNorm2d's mode (ir:394-395):
+        callers outside the module forward / GANStep pass the module's train()/eval() state.
+        bn_repeat: BatchNorm's running update applied that many times (BNLayer.repeat)."""
         B, _, H, W = ir_nchw.shape
         g, T = bufs or self.bufs, self.tdt
         train = self.training if training is None else bool(training)
+        if self.norm_type == "batch":
+            for n in self.norms.values():
+                n.configure(training=train, groups=1, repeat=bn_repeat)
         c0, c1, c2 = self.ngf, 2 * self.ngf, 4 * self.ngf
         H1, W1, H2, W2 = self._dims(H, W)
         g.state["shape"] = (B, H, W)
@@ -875,7 +1020,9 @@ class DiscriminatorEngine:
         self.chans = chans
         self.packs = [_pc(store, k, ConvSpec(chans[i], chans[i + 1], 4, s, 1, PAD_ZERO), dtype)
                       for i, (k, s, _) in enumerate(self.LAYERS)]
-        self.norms = [make_norm(norm) if n else None for (_, _, n) in self.LAYERS]
+        self.norms = [make_norm(norm, store, f"model.{int(k.split('.')[1]) + 1}") if n else None
+                      for (k, _, n) in self.LAYERS]
+        self.norm_type, self.training = norm, True
         self.bufs = Buffers(store.device)
 
     def pack(self):
@@ -883,10 +1030,16 @@ class DiscriminatorEngine:
             self._pack_batch = ops.PackBatch(self.packs)
         self._pack_batch.run()
 
-    def forward(self, din: Feat, tag="", bufs: Buffers = None) -> torch.Tensor:
+    def forward(self, din: Feat, tag="", bufs: Buffers = None, groups: int = 1) -> torch.Tensor:
         """din: NHWC (NB, H, W, 4) compute-dtype -> patch logits (NB, h, w, 1) fp32.
-        The activations are kept in ``bufs`` (default: the engine's own) under ``tag``."""
+        The activations are kept in ``bufs`` (default: the engine's own) under ``tag``.
+        groups: BatchNorm statistics per group of NB / groups samples (BNLayer.groups);
+        self.training: BatchNorm's train() / eval() mode."""
         g, T = bufs or self.bufs, self.tdt
+        if self.norm_type == "batch":
+            for nrm in self.norms:
+                if nrm is not None:
+                    nrm.configure(training=self.training, groups=groups, repeat=1)
         x = din
         acts, pre = [din], {}
         g.state[tag] = (acts, pre)
@@ -934,7 +1087,8 @@ class DiscriminatorEngine:
                     bias_sum = Feat(dout)
             elif self.norms[i] is not None:
                 self.norms[i].bwd(g, f"{tag}n{i}", dy, pre[i], ACT_LRELU, dy,
-                                  db=S.krsc(key + ".bias", G) if want_wgrad and key + ".bias" in S.shapes else None)
+                                  db=S.krsc(key + ".bias", G) if want_wgrad and key + ".bias" in S.shapes else None,
+                                  wgrad=want_wgrad)
             elif want_wgrad:  # layer 0: LReLU mask already folded into dy by the layer-1 dgrad
                 bias_sum = dy
             if want_wgrad:
@@ -1275,9 +1429,11 @@ class GANStep:
         # ---- G forward once: ir:1638 and ir:1657 compute the same image -- unless G has
         # dropout, whose two calls draw two masks: then the D step gets its own forward
         # (ir:1638-1639, under no_grad: its activations are never read back)
-        self.gen.training = True
+        # BatchNorm: the one forward stands for the reference's two training-mode forwards, so its
+        # running update is applied twice (with dropout the two forwards update once each)
+        self.gen.training = self.dis.training = True
         fake_d = self.gen.forward(ir, bufs=self.dbufs) if self.gen.use_dropout else None
-        fake = self.gen.forward(ir)
+        fake = self.gen.forward(ir, bn_repeat=1 if self.gen.use_dropout else 2)
         # ---- D step on [real; fake] as one 2B batch (ir:1636-1651), on the side stream
         dfake = b.get("dfake", (B, H, W, cout), torch.float32)
 
@@ -1319,7 +1475,7 @@ class GANStep:
             # -0.8 %: the G forward slowed by what it took off the join, profiles/r05_ab1_dsplit.txt)
             self.D.zero_grad()
             ops.axpby(Feat(fake if fake_d is None else fake_d), 1.0, Feat(din.t[B:], cin, cout))
-            pred = self.dis.forward(din, tag="d")
+            pred = self.dis.forward(din, tag="d", groups=2)   # BatchNorm: netD(real), netD(fake) statistics
             dpred = b.get("dpred", tuple(pred.shape), torch.float32)
             ops.hinge(pred, pred[:B].numel(), 0, 1.0, dpred, L[0:1])
             # D grads reduced tail-first under the D backward (8 MB buckets: model.8 + the head

@@ -113,7 +113,9 @@ class Identity(nn.Module):
 
 
 def get_norm_layer(norm_type="instance"):
-    """ir:154-165.  The HIP path implements 'instance' (the reference default)."""
+    """ir:154-165.  The HIP engines implement all three: 'instance' (the reference default),
+    'none' and 'batch' (nn.BatchNorm2d on one device: engine.BNLayer; with more than one
+    data-parallel rank it would have to be SyncBN, which GANTrainer refuses)."""
     if norm_type == "batch":
         return nn.BatchNorm2d
     if norm_type == "instance":
@@ -125,14 +127,13 @@ def get_norm_layer(norm_type="instance"):
 
 def _norm_name(norm_layer):
     """The engine norm for a reference norm_layer (ir:154-165): nn.InstanceNorm2d ->
-    'instance', get_norm_layer('none')'s Identity factory -> 'none'.  nn.BatchNorm2d
-    needs cross-sample statistics (SyncBN under data parallelism): out of scope."""
+    'instance', nn.BatchNorm2d -> 'batch' (either one also as a functools.partial),
+    get_norm_layer('none')'s Identity factory -> 'none'."""
     f = norm_layer.func if isinstance(norm_layer, functools.partial) else norm_layer
     if f is nn.InstanceNorm2d:
         return "instance"
     if f is nn.BatchNorm2d:
-        raise NotImplementedError("norm='batch' is out of scope for the HIP engines (SURVEY.md 8e); "
-                                  "use 'instance' (the reference default) or 'none'")
+        return "batch"
     try:
         probe = norm_layer(4)
     except Exception:
@@ -143,8 +144,9 @@ def _norm_name(norm_layer):
 
 
 def init_weights(net, init_type="normal", init_gain=0.02, generator=None):
-    """ir:168-198: conv weights ~ N(0, gain) (normal), bias 0.  Writes through the
-    OIHW parameter views into the flat device buffers."""
+    """ir:168-198: conv weights ~ N(0, gain) (normal), BatchNorm2d weights ~ N(1, gain)
+    (ir:192-196), bias 0; drawn from ``generator`` in named_parameters() order.  Writes
+    through the OIHW parameter views into the flat device buffers."""
     with torch.no_grad():
         for name, p in net.named_parameters():
             if name.endswith(".weight") and p.dim() == 4:
@@ -160,6 +162,8 @@ def init_weights(net, init_type="normal", init_gain=0.02, generator=None):
                 else:
                     raise NotImplementedError(f"init method [{init_type}] is not implemented")
                 p.copy_(w)
+            elif name.endswith(".weight") and p.dim() == 1:   # nn.BatchNorm2d's scale
+                p.copy_(torch.empty(p.shape).normal_(1.0, init_gain, generator=generator))
             elif name.endswith(".bias"):
                 p.zero_()
     if hasattr(net, "repack"):
@@ -236,6 +240,23 @@ class _Slot(nn.Module):
         self.weight = nn.Parameter(store.oihw(key + ".weight"))
         if key + ".bias" in store.shapes:   # use_bias (ir:450-455, 588-593)
             self.bias = nn.Parameter(store.oihw(key + ".bias"))
+
+
+class _BNSlot(nn.Module):
+    """nn.BatchNorm2d's parameters (views into the ParamStore) and buffers (the store's own
+    tensors, which the kernels update in place) at the reference's module position."""
+
+    def __init__(self, store: ParamStore, key: str):
+        super().__init__()
+        self.weight = nn.Parameter(store.oihw(key + ".weight"))
+        self.bias = nn.Parameter(store.oihw(key + ".bias"))
+        for b in ("running_mean", "running_var", "num_batches_tracked"):
+            self.register_buffer(b, store.buffers[f"{key}.{b}"])
+
+
+def _norm_slot(store: ParamStore, key: str):
+    """The norm module at state key ``key``: a _BNSlot under norm='batch', else nothing."""
+    return _BNSlot(store, key) if key + ".running_mean" in store.buffers else None
 
 
 class _Filt(nn.Module):
@@ -324,25 +345,26 @@ class ResnetUNetGenerator(_StoreModule):
         device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
         self.store = ParamStore(g_param_shapes(input_nc, output_nc, ngf, n_blocks, no_antialias, no_antialias_up,
                                                use_bias=norm == "instance", padding_type=padding_type,
-                                               use_dropout=use_dropout), device)
+                                               use_dropout=use_dropout, batch_norm=norm == "batch"), device)
         S = self.store
-        self.inc = _seq(None, _Slot(S, "inc.1"), None, None)
-        self.down1 = _seq(_Slot(S, "down1.0"), None, None)
+        self.inc = _seq(None, _Slot(S, "inc.1"), _norm_slot(S, "inc.2"), None)
+        self.down1 = _seq(_Slot(S, "down1.0"), _norm_slot(S, "down1.1"), None)
         self.down1_down = None if no_antialias else _Filt(2 * ngf, device)
-        self.down2 = _seq(_Slot(S, "down2.0"), None, None)
+        self.down2 = _seq(_Slot(S, "down2.0"), _norm_slot(S, "down2.1"), None)
         self.down2_down = None if no_antialias else _Filt(4 * ngf, device)
         blocks = []
         nmods = k2 + 2   # [pad] conv norm relu [dropout] [pad] conv norm (ir:375-411)
         for b in range(n_blocks):
             blk = nn.Module()
-            blk.conv_block = _seq(*[_Slot(S, f"resblocks.{b}.conv_block.{i}") if i in (k1, k2) else None
+            blk.conv_block = _seq(*[_Slot(S, f"resblocks.{b}.conv_block.{i}") if i in (k1, k2) else
+                                    (_norm_slot(S, f"resblocks.{b}.conv_block.{i}") if i in (k1 + 1, k2 + 1) else None)
                                     for i in range(nmods)])
             blocks.append(blk)
         self.resblocks = nn.Sequential(*blocks)
         self.up1_up = _Slot(S, "up1_up") if no_antialias_up else _Filt(4 * ngf, device)
-        self.up1_conv = _seq(_Slot(S, "up1_conv.0"), None, None)
+        self.up1_conv = _seq(_Slot(S, "up1_conv.0"), _norm_slot(S, "up1_conv.1"), None)
         self.up2_up = _Slot(S, "up2_up") if no_antialias_up else _Filt(2 * ngf, device)
-        self.up2_conv = _seq(_Slot(S, "up2_conv.0"), None, None)
+        self.up2_conv = _seq(_Slot(S, "up2_conv.0"), _norm_slot(S, "up2_conv.1"), None)
         self.outc = _seq(None, _Slot(S, "outc.1"), None)
         self.engine = GeneratorEngine(S, _dtype_code(compute_dtype), ngf=ngf, input_nc=input_nc,
                                       output_nc=output_nc, n_blocks=n_blocks, no_antialias=no_antialias,
@@ -398,7 +420,9 @@ class _DFn(torch.autograd.Function):
 
 
 class NLayerDiscriminator(_StoreModule):
-    """ir:576-635: any n_layers >= 1 (train_kaist builds 3), norm 'instance' or 'none'."""
+    """ir:576-635: any n_layers >= 1 (train_kaist builds 3), norm 'instance', 'none' or 'batch'.
+    Under norm='batch' every call normalises with its own batch's statistics and updates the
+    running buffers once (netD(real), netD(fake): two updates, ir:1642-1643)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.InstanceNorm2d, device=None,
                  compute_dtype="bf16"):
@@ -406,11 +430,13 @@ class NLayerDiscriminator(_StoreModule):
         assert n_layers >= 1
         norm = _norm_name(norm_layer)
         device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-        self.store = ParamStore(d_param_shapes(input_nc, ndf, n_layers, use_bias=norm == "instance"), device)
+        self.store = ParamStore(d_param_shapes(input_nc, ndf, n_layers, use_bias=norm == "instance",
+                                               batch_norm=norm == "batch"), device)
         S = self.store
         keys = [k for k, _, _ in d_layers(n_layers)]
         last = int(keys[-1].split(".")[1])
-        self.model = _seq(*[_Slot(S, f"model.{i}") if f"model.{i}" in keys else None for i in range(last + 1)])
+        self.model = _seq(*[_Slot(S, f"model.{i}") if f"model.{i}" in keys else _norm_slot(S, f"model.{i}")
+                            for i in range(last + 1)])
         self.engine = DiscriminatorEngine(S, _dtype_code(compute_dtype), input_nc=input_nc, ndf=ndf,
                                           n_layers=n_layers, norm=norm)
         self._dirty = True
@@ -418,6 +444,7 @@ class NLayerDiscriminator(_StoreModule):
     def forward(self, x):
         _require_cuda(x, "NLayerDiscriminator")
         self.repack()
+        self.engine.training = self.training   # nn.BatchNorm2d follows train() / eval()
         params = [p for _, p in self.named_parameters()]
         if torch.is_grad_enabled():
             return _DFn.apply(x, self, *params)
@@ -598,6 +625,19 @@ class IRColorizationModel(nn.Module):
 # fused train step (the hot path) + train / validation drivers (ir:1521-1723)
 # =============================================================================
 
+def _refuse_multi_rank_batch_norm(cfg, process_group=None):
+    """norm='batch' normalises with the LOCAL batch's statistics: with more than one
+    data-parallel rank the reference semantics need SyncBN, which is not implemented."""
+    import torch.distributed as dist
+    if getattr(cfg, "norm", "instance") != "batch" or not (dist.is_available() and dist.is_initialized()):
+        return
+    world = dist.get_world_size(process_group)
+    if world > 1:
+        raise NotImplementedError(f"norm='batch' with {world} data-parallel ranks needs SyncBN (statistics over the "
+                                  "global batch), which the HIP engines do not implement: train on one device, or "
+                                  "use norm='instance' / 'none'")
+
+
 class GANTrainer:
     """Owns G (through the model), D, VGG and both Adams; ``step(ir, rgb)`` runs
     the fused HIP train step and returns the device loss vector (no host sync)."""
@@ -607,6 +647,7 @@ class GANTrainer:
         """force_reduce: the data-parallel gradient collectives run even at world size 1
         (engine.BucketedAllreduce; needs an initialised process group)."""
         self.cfg = cfg
+        _refuse_multi_rank_batch_norm(cfg, process_group)   # before any GPU work
         dev = torch.device(cfg.device)
         dt = getattr(cfg, "compute_dtype", "bf16")
         if getattr(cfg, "deterministic", False):
@@ -645,7 +686,8 @@ class GANTrainer:
 
     # ---- full training state.  The reference checkpoints G only
     # (ir:1708); this adds D, both Adams (torch.optim.Adam.state_dict() layout) and
-    # the LambdaLR position, so an interrupted run resumes bit-exactly.
+    # the LambdaLR position, so an interrupted run resumes bit-exactly.  Under norm='batch'
+    # the networks' entries carry running_mean / running_var / num_batches_tracked too.
     def state_dict(self):
         c, s = self.cfg, self.core
         return {"netG": {k: v.detach().cpu().clone() for k, v in self.netG.store.state().items()},

@@ -643,6 +643,54 @@ def channel_sum(g: Feat, db: torch.Tensor):
 
 
 # ----------------------------------------------------------------------------
+# batch norm (csrc/batchnorm.hip): per-channel statistics over groups of samples
+# ----------------------------------------------------------------------------
+
+NORM_AFFINE = _lib.header_enum("IRGAN_NORM_AFFINE")   # OR-ed into act: the table is BatchNorm's {shift, scale}
+BN_TABLE = _lib.header_enum("IRGAN_BN_TABLE")         # floats per (n, c) of the statistics table
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1                       # nn.BatchNorm2d's defaults (ir:158-159)
+
+
+def bn_stats(x: Feat, work: torch.Tensor, mr: torch.Tensor, groups=1, gamma=None, beta=None, running_mean=None,
+             running_var=None, repeat=1, ab=None, nb=0):
+    """Training-mode statistics of x per (group, channel): mr[n][c] = {mean, rstd, mean_lo, 0}
+    (BN_TABLE floats; each sample carries its group's entry) and, with ``ab``, the {shift, scale} table of the fused resample
+    consumers.  nb > 0: ``work`` already holds nb {sum, sum of squares} partials per image
+    (conv_fwd_stats); else a statistics pass over x runs first.  running_mean / running_var
+    (optional) are updated in place, group after group, each ``repeat`` times."""
+    assert x.N % groups == 0 and repeat >= 1
+    if nb:
+        _lib.call("irgan_bn_finalize", P(work), x.N, x.H * x.W, x.C, nb, groups, P(gamma), P(beta), P(running_mean),
+                  P(running_var), BN_MOMENTUM, BN_EPS, repeat, P(mr), P(ab), stream())
+    else:
+        _lib.call("irgan_bn_stats", x.ptr, x.dt, x.N, x.H * x.W, x.C, x.ld, x.off, groups, P(gamma), P(beta),
+                  P(running_mean), P(running_var), BN_MOMENTUM, BN_EPS, repeat, P(work), P(mr), P(ab), stream())
+
+
+def bn_eval_table(running_mean, running_var, gamma, beta, N: int, mr: torch.Tensor, ab=None):
+    """Eval mode: the mr (and ab) tables of N samples from the running statistics."""
+    _lib.call("irgan_bn_eval_table", P(running_mean), P(running_var), P(gamma), P(beta), N, running_mean.numel(),
+              BN_EPS, P(mr), P(ab), stream())
+
+
+def bn_apply(x: Feat, mr, gamma, beta, y: Feat, act=ACT_NONE, res: Feat = None):
+    """y = act(gamma * (x - mean) * rstd + beta) [+ res]."""
+    assert x.dt == y.dt and (res is None or res.dt == x.dt)
+    _lib.call("irgan_bn_apply", x.ptr, x.dt, x.N, x.H * x.W, x.C, x.ld, x.off, P(mr), P(gamma), P(beta), act,
+              res.ptr if res else None, res.ld if res else 0, res.off if res else 0, y.ptr, y.ld, y.off, stream())
+
+
+def bn_backward(dy: Feat, x: Feat, act: int, mr, gamma, beta, work, red, dx: Feat, dgamma=None, dbeta=None, groups=1,
+                eval_mode=False, dy2: Feat = None):
+    """dx = backward of act(BN(x)) applied to (dy [+ dy2]); x = PRE-norm input; dgamma / dbeta
+    (fp32, optional) are accumulated.  eval_mode: mr holds the running statistics."""
+    d2 = (dy2.ptr, dy2.dt, dy2.ld, dy2.off) if dy2 is not None else (None, 0, 0, 0)
+    _lib.call("irgan_bn_backward", dy.ptr, dy.dt, dy.ld, dy.off, *d2, x.ptr, x.dt, x.ld, x.off, act, x.N, x.H * x.W,
+              x.C, groups, int(eval_mode), P(mr), P(gamma), P(beta), P(work), P(red), dx.ptr, dx.dt, dx.ld, dx.off,
+              P(dgamma), P(dbeta), stream())
+
+
+# ----------------------------------------------------------------------------
 # resampling / elementwise
 # ----------------------------------------------------------------------------
 
