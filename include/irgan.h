@@ -227,6 +227,24 @@ IRGAN_API int irgan_in_bwd_apply(const void* dy, int32_t dy_dtype, int32_t lddy,
                        int32_t N, int32_t HW, int32_t C, const float* mr, const float* red,
                        void* dx, int32_t dx_dtype, int32_t lddx, int32_t dxoff, float* db,
                        irgan_stream_t s);
+/* irgan_in_bwd_reduce + irgan_in_bwd_apply in ONE launch for maps that fit a CU's
+ * registers: a workgroup owns IRGAN_IN_ONEPASS_CG channels of one image, reads dy and x
+ * once, reduces, writes red[n][c] = {mean g, mean g*xhat} (an OUTPUT here; fp32, the
+ * values dx is computed from) and dx.  Deterministic; dx may alias dy.  bf16 only.
+ * red and dx are bit for bit what irgan_in_bwd_reduce + irgan_in_bwd_apply write for the
+ * same arguments: the sums are grouped as the reduce pass and its finalize group them.
+ * IRGAN_EUNSUPPORTED (nothing launched, nothing written) unless every tensor is bf16,
+ * dy2 == NULL, HW * IRGAN_IN_ONEPASS_CG <= IRGAN_IN_ONEPASS_ELEMS, C is a multiple of
+ * IRGAN_IN_ONEPASS_CG and every ld / off is a multiple of 8 -- and, beyond those, where the
+ * reduce pass's row partition at (N, HW, C) gives a thread more than 16 pixels or the group
+ * more than 512 threads (batches of several hundred images, C >= 2048). */
+enum { IRGAN_IN_ONEPASS_CG = 16, IRGAN_IN_ONEPASS_ELEMS = 65536 };
+IRGAN_API int irgan_in_bwd_onepass(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff,
+                         const void* dy2, int32_t dy2_dtype, int32_t lddy2, int32_t dy2off,
+                         const void* x, int32_t x_dtype, int32_t ldx, int32_t xoff, int32_t act,
+                         int32_t N, int32_t HW, int32_t C, const float* mr, float* red,
+                         void* dx, int32_t dx_dtype, int32_t lddx, int32_t dxoff,
+                         irgan_stream_t s);
 
 /* irgan_in_apply (bf16 x, res, y) / irgan_in_bwd_apply (bf16, no db) that also
  * write y8 = e4m3(clamp(bf16(y) * q[0], +-448)) (an NHWC fp8 slice) and record
@@ -242,6 +260,14 @@ IRGAN_API int irgan_in_bwd_apply_fp8(const void* dy, int32_t lddy, int32_t dyoff
                            int32_t HW, int32_t C, const float* mr, const float* red, void* dx, int32_t lddx,
                            int32_t dxoff, void* y8, int32_t ld8, int32_t off8, const float* q,
                            uint32_t* amax, irgan_stream_t s);
+/* irgan_in_bwd_onepass that also writes the fp8 copy of dx and its amax (as
+ * irgan_in_bwd_apply_fp8 does: the same bytes irgan_fp8_quant makes of the stored dx);
+ * red is an output.  The legality of irgan_in_bwd_onepass, ld8 / off8 included. */
+IRGAN_API int irgan_in_bwd_onepass_fp8(const void* dy, int32_t lddy, int32_t dyoff, const void* dy2, int32_t lddy2,
+                             int32_t dy2off, const void* x, int32_t ldx, int32_t xoff, int32_t act, int32_t N,
+                             int32_t HW, int32_t C, const float* mr, float* red, void* dx, int32_t lddx,
+                             int32_t dxoff, void* y8, int32_t ld8, int32_t off8, const float* q,
+                             uint32_t* amax, irgan_stream_t s);
 /* db[c] += sum over pixels of g[p][c] (bias gradient), g slice (dtype, ld, off).
  * work: 16*IRGAN_IN_PARTS*C doubles of scratch. */
 IRGAN_API int irgan_channel_sum(const void* g, int32_t dtype, int32_t P, int32_t C, int32_t ld,

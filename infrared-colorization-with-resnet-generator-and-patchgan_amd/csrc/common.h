@@ -145,6 +145,12 @@ IRGAN_HD int xcd_tile(int b, int nb, int swz) {
     if (!swz || (nb & 7)) return b;
     return (b & 7) * (nb >> 3) + (b >> 3);
 }
+// The same for any grid size: XCD x (blocks b % 8 == x) takes a contiguous range of
+// logical tiles (xcd_tile needs nb % 8 == 0)
+IRGAN_HD int xcd_tile_any(int b, int nb) {
+    const int x = b & 7, k = b >> 3, per = nb >> 3, rem = nb & 7;
+    return x * per + (x < rem ? x : rem) + k;
+}
 
 #define IRGAN_LAUNCH_CHECK()                    \
     do {                                          \

@@ -374,13 +374,6 @@ constexpr int W2_STAGES = 4;                 // 136 KiB
 #define W2_EXP 0
 #endif
 
-// XCD-aware order for any grid size: XCD x (blocks b % 8 == x) takes a contiguous range of
-// logical tiles (xcd_tile needs nb % 8 == 0)
-IRGAN_HD int xcd_tile_any(int b, int nb) {
-    const int x = b & 7, k = b >> 3, per = nb >> 3, rem = nb & 7;
-    return x * per + (x < rem ? x : rem) + k;
-}
-
 __global__ __launch_bounds__(W2_NT, 1) void wgrad_w2_kernel(const irgan_conv_desc d, const bf16_t* __restrict__ x,
                                                             const bf16_t* __restrict__ dy, float* __restrict__ dw,
                                                             int segs_per_block, int nseg, int ntco, int nci2, int swz,

@@ -623,6 +623,248 @@ int launch_rows(Slice X, Slice DY, Slice DY2, int act, const float* mr, const fl
     return 0;
 }
 
+// One-pass InstanceNorm backward for maps that fit one CU's registers.  InstanceNorm is
+// independent per (image, channel), so a workgroup owns (image n, CG consecutive channels)
+// instead of a run of rows: it loads its slices of x and dy once (every 16-byte load of the
+// slice issued before any is used), reduces sum g and sum g*xhat itself, and writes dx from
+// the registers it holds -- 6 bytes per element where reduce + finalize + apply move 10, and
+// no partials, finalize launch, ticket or wait on another block.
+// The result is the three launches' bit for bit: the sums are grouped exactly as
+// rows8_kernel<1> + finalize_kernel group them at the same (N, HW, C).  There, block b of nb
+// covers `rows` rows, its thread (rl, channel lane) adds rows r0 + rl, r0 + rl + RP, ... in
+// order (a chain), block_partials8 combines the RP chains of a channel (a butterfly inside
+// each wave then the four waves in order, or the RP chains in order when the channel lanes do
+// not divide a wave), and finalize_kernel adds the nb partials in fp64 (partial b in lane
+// b % FS, the lanes in order).  Here a thread owns one chain of one channel octet (CG / 8
+// octets): it holds the chain's <= U pixels, sums them in the same order with the same float
+// operations (the fused multiply-adds rows8_kernel compiles to are written out), the chains meet in LDS and are combined in that order, and the fp32 {mean g,
+// mean g*xhat} stored to red are the values dx is computed from.  Tail items re-load a valid
+// pixel with dy = 0 (they add +-0).  Deterministic; no atomics but the amax record.  The
+// barriers of the reduction sit between a workgroup's last load and its first store and it
+// stores only pixels it loaded, so dx may alias dy.
+// Logical group t = n * (C / CG) + cg runs on XCD blockIdx.x % 8 in contiguous ranges
+// (xcd_tile_any): the 64 / CG groups that share the 128-byte lines of one image sit in
+// adjacent dispatch slots of one L2.  Speed only, but all of it: in plain blockIdx order the
+// four groups of a line sit on four XCDs and the launch takes twice as long.
+// At most 512 threads (a full map: 256 chains of 16 pixels per octet, 214 VGPRs, no scratch).
+// IN_ONEPASS_CG: variant builds (tools/build_variant.sh) for tools/norm_bench.py; CG = 8 reads
+// 16-byte segments and is slower, CG = 32 holds 2048 px (profiles/in_bwd_onepass_bench.txt)
+#ifndef IN_ONEPASS_CG
+#define IN_ONEPASS_CG IRGAN_IN_ONEPASS_CG
+#endif
+constexpr int OP_CG = IN_ONEPASS_CG;   // channels per workgroup: 8, 16 or 32
+constexpr int OP_MAXU = 16;            // pixels per chain: 16 x (x, dy) uint4 = 128 raw VGPRs per thread
+constexpr int OP_MAXNT = 512;
+constexpr int OP_CAP = IRGAN_IN_ONEPASS_ELEMS;   // elements of one (n, channel group) slice: 4096 px at CG = 16
+
+template <bool F8, int NT, int CG, int U>
+__global__ __launch_bounds__(NT) void in_bwd_onepass_kernel(const bf16_t* x, int ldx, int xoff, const bf16_t* dy,
+                                                            int lddy, int dyoff, int act,
+                                                            const float* __restrict__ mr, float* __restrict__ red,
+                                                            bf16_t* dx, int lddx, int dxoff, int HW, int C, int swz,
+                                                            int nb, int rows, int RP, Q8 q8) {
+    constexpr int LPP = CG / 8, NCH = NT / LPP;
+    static_assert(LPP == 1 || LPP == 2 || LPP == 4, "CG in {8, 16, 32}");
+    __shared__ float sc[NCH][CG * 2];        // chain sums: [chain][(channel, g | g*xhat)]
+    __shared__ float pt[IN_PARTS][CG * 2];   // the nb block partials of rows8_kernel<1>
+    __shared__ float sf[CG][2];              // {mean g, mean g*xhat}: the values stored to red
+    const int G = C / CG;
+    const int t = swz ? xcd_tile_any(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int n = t / G, cg = t - n * G;
+    const int h = threadIdx.x % LPP, q = threadIdx.x / LPP;   // channel octet, chain
+    const int b = q / RP, rl = q - b * RP;
+    const bool on = q < nb * RP;
+    const int r0 = b * rows + rl, r1 = on ? min(HW, (b + 1) * rows) : 0;   // the chain: r0, r0 + RP, ... < r1
+    // workgroup-uniform 64-bit bases (scalar registers) + 32-bit lane offsets inside the
+    // image (HW * ld < 2^30, checked by the launcher)
+    const long pb = (long)n * HW;
+    const bf16_t* xb = x + pb * ldx + xoff + cg * CG;
+    const bf16_t* gb = dy + pb * lddy + dyoff + cg * CG;
+    bf16_t* ob = dx + pb * lddx + dxoff + cg * CG;
+    const uint32_t h8 = h * 8;
+
+    uint4 xr[U], gr[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t p = min(r0 + u * RP, HW - 1);
+        xr[u] = *(const uint4*)(xb + (p * (uint32_t)ldx + h8));
+        gr[u] = *(const uint4*)(gb + (p * (uint32_t)lddy + h8));
+    }
+    // {mean, rstd} of the group's CG channels while those loads are in flight: the address is
+    // workgroup-uniform (constant address space: the kernel never writes the table), a lane
+    // selects its octet's entries
+    typedef const float __attribute__((address_space(4))) * cfloat_p;
+    const cfloat_p mrow = (cfloat_p)(uintptr_t)(mr + 2 * ((long)n * C + cg * CG));
+    float mean[8], rstd[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        mean[k] = mrow[2 * k];
+        rstd[k] = mrow[2 * k + 1];
+#pragma unroll
+        for (int j = 1; j < LPP; ++j) {
+            mean[k] = h == j ? mrow[2 * (j * 8 + k)] : mean[k];
+            rstd[k] = h == j ? mrow[2 * (j * 8 + k) + 1] : rstd[k];
+        }
+    }
+    // act_grad(xh, act) without its per-element branches on act: 1 where xh > 0, else `neg`
+    const float neg = act == IRGAN_ACT_RELU ? 0.f : act == IRGAN_ACT_LRELU ? 0.2f : 1.f;
+    float a0[8], a1[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { a0[k] = 0.f; a1[k] = 0.f; }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        // an item past the chain's end holds a valid pixel of the same channels: its dy becomes
+        // 0, so it adds +-0 to both sums (straight-line code; rows8_kernel breaks out instead)
+        if (r0 + u * RP >= r1) gr[u] = make_uint4(0u, 0u, 0u, 0u);
+        float xv[8], gv[8];
+        bf8f(xr[u], xv);
+        bf8f(gr[u], gv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            // the contractions rows8_kernel<1> compiles to, spelled out (left to the compiler
+            // here, the two sums pair into a packed add and g * xh is rounded before it)
+            const float xh = (xv[k] - mean[k]) * rstd[k];
+            const float f = xh > 0.f ? 1.f : neg;
+            a0[k] = __builtin_fmaf(gv[k], f, a0[k]);
+            a1[k] = __builtin_fmaf(gv[k] * f, xh, a1[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // one item's temporaries at a time (register budget)
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        sc[q][(h * 8 + k) * 2] = a0[k];
+        sc[q][(h * 8 + k) * 2 + 1] = a1[k];
+    }
+    __syncthreads();
+    // block_partials8 of block pbk for one (channel, sum): CL channel lanes of rows8_kernel
+    const int CL = min(C / 8, TPB);
+    const bool tree = CL <= 64 && (64 % CL) == 0;
+    for (int task = threadIdx.x; task < nb * CG * 2; task += NT) {
+        const int cw = task % (CG * 2), pbk = task / (CG * 2);
+        const int c0 = pbk * RP;
+        float tsum = 0.f;
+        if (tree) {
+            const int RW = RP / (TPB / 64);   // rows of one wave: the butterfly, then the waves in order
+            for (int j = 0; j < TPB / 64; ++j) {
+                for (int o = 1; o < RW; o <<= 1)
+                    for (int i = 0; i < RW; i += 2 * o) sc[c0 + j * RW + i][cw] += sc[c0 + j * RW + i + o][cw];
+                tsum += sc[c0 + j * RW][cw];
+            }
+        } else {
+            for (int j = 0; j < RP; ++j) tsum += sc[c0 + j][cw];
+        }
+        pt[pbk][cw] = tsum;
+    }
+    __syncthreads();
+    if (threadIdx.x < CG * 2) {   // finalize_kernel: partial pbk in lane pbk % FS, then the lanes in order
+        const int cw = threadIdx.x;
+        double s = 0.0;
+        for (int k = 0; k < FS; ++k) {
+            double l = 0.0;
+            for (int pbk = k; pbk < nb; pbk += FS) l += pt[pbk][cw];
+            s += l;
+        }
+        const float v = (float)(s / HW);
+        sf[cw >> 1][cw & 1] = v;
+        red[2 * ((long)n * C + cg * CG) + cw] = v;
+    }
+    __syncthreads();
+    float mg[8], mgx[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { mg[k] = sf[h * 8 + k][0]; mgx[k] = sf[h * 8 + k][1]; }
+
+    const float qs = F8 ? *q8.q : 1.f;
+    float amx = 0.f;
+    uint8_t* qb = F8 ? q8.p + pb * q8.ld + q8.off + cg * CG : nullptr;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        // opaque to the optimiser: xhat and g are recomputed from the 8 raw registers, not kept
+        // from the first phase as 16 floats per item (there is no room for them)
+        asm volatile("" : "+v"(xr[u].x), "+v"(xr[u].y), "+v"(xr[u].z), "+v"(xr[u].w));
+        asm volatile("" : "+v"(gr[u].x), "+v"(gr[u].y), "+v"(gr[u].z), "+v"(gr[u].w));
+        const uint32_t p = r0 + u * RP;
+        if ((int)p >= r1) break;
+        float xv[8], gv[8], o[8];
+        bf8f(xr[u], xv);
+        bf8f(gr[u], gv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            // rstd * (g - mg - xh * mgx) as rows8_kernel<2> compiles it: two fused steps
+            const float xh = (xv[k] - mean[k]) * rstd[k];
+            const float f = xh > 0.f ? 1.f : neg;
+            o[k] = rstd[k] * __builtin_fmaf(-xh, mgx[k], __builtin_fmaf(gv[k], f, -mg[k]));
+        }
+        uint4 w;
+        w.x = pk_bf16(o[0], o[1]);
+        w.y = pk_bf16(o[2], o[3]);
+        w.z = pk_bf16(o[4], o[5]);
+        w.w = pk_bf16(o[6], o[7]);
+        *(uint4*)(ob + (p * (uint32_t)lddx + h8)) = w;
+        if constexpr (F8) {
+            float vb[8];
+            bf8f(w, vb);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) amx = fmaxf(amx, fabsf(vb[k]));
+            *(uint2*)(qb + (p * (uint32_t)q8.ld + h8)) = pack8_fp8(vb, qs);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (F8) fp8_block_amax(amx, q8.amax, blockIdx.x);
+}
+
+// The reduce pass's partition at (N, HW, C) (launch_rows<1>): nb blocks of `rows` rows, RP
+// chains each.  False when a chain is longer than OP_MAXU pixels or the chains of the
+// group's octets outnumber OP_MAXNT threads (batches of several hundred images, C >= 2048).
+struct OnepassPlan {
+    int nb, rows, RP, chain, threads;
+};
+bool onepass_plan(int N, int HW, int C, OnepassPlan* pl) {
+    pl->RP = rp_of(C, 8);
+    int nb = blocks_per_image(HW, N, pl->RP, pass_rpt(1, PASS_RPT[1]));
+    pl->rows = irgan_cdiv(HW, nb);
+    pl->nb = irgan_cdiv(HW, pl->rows);
+    pl->chain = irgan_cdiv(pl->rows, pl->RP);
+    pl->threads = pl->nb * pl->RP * (OP_CG / 8);
+    return pl->chain <= OP_MAXU && pl->threads <= OP_MAXNT && pl->nb <= IN_PARTS;
+}
+
+// legal: all-bf16 callers only (the entry points take no dtypes), the slice fits the
+// registers in the reduce pass's partition, whole channel groups, 16-byte lanes
+bool onepass_ok(int N, int HW, int C, std::initializer_list<int> lds) {
+    if (N < 0 || HW < 0 || C < 0 || C % OP_CG || (long)HW * OP_CG > OP_CAP) return false;
+    for (int l : lds)
+        if (l % 8 || l < 0 || (long)HW * l >= (1L << 30)) return false;   // 32-bit lane offsets
+    OnepassPlan pl;
+    return (long)N * HW * C <= 0 || onepass_plan(N, HW, C, &pl);
+}
+
+template <bool F8, int NT>
+void onepass_nt(const OnepassPlan& pl, dim3 g, hipStream_t st, const bf16_t* x, int ldx, int xoff, const bf16_t* dy,
+                int lddy, int dyoff, int act, const float* mr, float* red, bf16_t* dx, int lddx, int dxoff, int HW,
+                int C, Q8 q8) {
+    const int swz = irgan_xcd_swz();
+#define OP_GO(U_)                                                                                                    \
+    in_bwd_onepass_kernel<F8, NT, OP_CG, U_><<<g, NT, 0, st>>>(x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, \
+                                                                dxoff, HW, C, swz, pl.nb, pl.rows, pl.RP, q8)
+    if (pl.chain <= 1) OP_GO(1);
+    else if (pl.chain <= 2) OP_GO(2);
+    else if (pl.chain <= 4) OP_GO(4);
+    else if (pl.chain <= 8) OP_GO(8);
+    else OP_GO(16);
+#undef OP_GO
+}
+
+template <bool F8>
+void onepass_go(const bf16_t* x, int ldx, int xoff, const bf16_t* dy, int lddy, int dyoff, int act, const float* mr,
+                float* red, bf16_t* dx, int lddx, int dxoff, int N, int HW, int C, hipStream_t st, Q8 q8) {
+    OnepassPlan pl;
+    onepass_plan(N, HW, C, &pl);
+    const dim3 g(N * (C / OP_CG));
+    if (pl.threads <= 128) onepass_nt<F8, 128>(pl, g, st, x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, dxoff, HW, C, q8);
+    else if (pl.threads <= 256) onepass_nt<F8, 256>(pl, g, st, x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, dxoff, HW, C, q8);
+    else onepass_nt<F8, 512>(pl, g, st, x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, dxoff, HW, C, q8);
+}
+
 }  // namespace
 
 extern "C" int irgan_in_stats(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ld,
@@ -719,6 +961,38 @@ extern "C" int irgan_in_bwd_apply(const void* dy, int32_t dy_dtype, int32_t lddy
     Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
     launch_rows<2>(X, DY, DY2, act, mr, red, dx, dx_dtype, lddx, dxoff, N, HW, C, nullptr, db, vec, (hipStream_t)s,
                    nullptr);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_in_bwd_onepass(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff, const void* dy2,
+                                    int32_t dy2_dtype, int32_t lddy2, int32_t dy2off, const void* x, int32_t x_dtype,
+                                    int32_t ldx, int32_t xoff, int32_t act, int32_t N, int32_t HW, int32_t C,
+                                    const float* mr, float* red, void* dx, int32_t dx_dtype, int32_t lddx,
+                                    int32_t dxoff, irgan_stream_t s) {
+    (void)dy2_dtype; (void)lddy2; (void)dy2off;
+    if (!dy || !x || !mr || !red || !dx) return IRGAN_EINVAL;
+    if (dy2 || dy_dtype != IRGAN_BF16 || x_dtype != IRGAN_BF16 || dx_dtype != IRGAN_BF16 ||
+        !onepass_ok(N, HW, C, {lddy, dyoff, ldx, xoff, lddx, dxoff}))
+        return IRGAN_EUNSUPPORTED;
+    if ((long)N * HW * C <= 0) return 0;
+    onepass_go<false>((const bf16_t*)x, ldx, xoff, (const bf16_t*)dy, lddy, dyoff, act, mr, red, (bf16_t*)dx, lddx,
+                      dxoff, N, HW, C, (hipStream_t)s, Q8{});
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_in_bwd_onepass_fp8(const void* dy, int32_t lddy, int32_t dyoff, const void* dy2, int32_t lddy2,
+                                        int32_t dy2off, const void* x, int32_t ldx, int32_t xoff, int32_t act,
+                                        int32_t N, int32_t HW, int32_t C, const float* mr, float* red, void* dx,
+                                        int32_t lddx, int32_t dxoff, void* y8, int32_t ld8, int32_t off8,
+                                        const float* q, uint32_t* amax, irgan_stream_t s) {
+    (void)lddy2; (void)dy2off;
+    if (!dy || !x || !mr || !red || !dx || !y8 || !q || !amax) return IRGAN_EINVAL;
+    if (dy2 || !onepass_ok(N, HW, C, {lddy, dyoff, ldx, xoff, lddx, dxoff, ld8, off8})) return IRGAN_EUNSUPPORTED;
+    if ((long)N * HW * C <= 0) return 0;
+    onepass_go<true>((const bf16_t*)x, ldx, xoff, (const bf16_t*)dy, lddy, dyoff, act, mr, red, (bf16_t*)dx, lddx,
+                     dxoff, N, HW, C, (hipStream_t)s, Q8{(uint8_t*)y8, ld8, off8, q, amax});
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

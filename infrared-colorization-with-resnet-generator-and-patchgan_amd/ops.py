@@ -624,8 +624,71 @@ def in_bwd_parts(dy: Feat, x: Feat, act: int, mr, work, red, dx: Feat, db=None, 
     return reduce, apply
 
 
+IN_ONEPASS_CG = _lib.header_enum("IRGAN_IN_ONEPASS_CG")        # channels per workgroup
+IN_ONEPASS_ELEMS = _lib.header_enum("IRGAN_IN_ONEPASS_ELEMS")  # elements of one workgroup's slice
+# the one-pass InstanceNorm backward where it is legal and fills the chip;
+# IRGAN_IN_BWD_ONEPASS=0: always reduce + finalize + apply (the A/B switch)
+IN_BWD_ONEPASS = [os.environ.get("IRGAN_IN_BWD_ONEPASS") != "0"]
+_CUS = {}
+
+
+def _cu_count(dev) -> int:
+    c = _CUS.get(dev)
+    if c is None:
+        c = _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return c
+
+
+def in_bwd_onepass_legal(N, HW, C, dts, lds, has_db=False, has_dy2=False) -> bool:
+    """What irgan_in_bwd_onepass accepts: dts the dtype codes of dy, x and dx, lds every
+    ld and off of theirs."""
+    return (all(d == BF16 for d in dts) and not has_db and not has_dy2 and C % IN_ONEPASS_CG == 0
+            and HW * IN_ONEPASS_CG <= IN_ONEPASS_ELEMS and all(v % 8 == 0 for v in lds))
+
+
+def in_bwd_use_onepass(N, HW, C, dts, lds, cus, has_db=False, has_dy2=False, q8=None) -> bool:
+    """in_backward's choice between the one-pass kernel and the three row-split launches:
+    one-pass when it is legal and its N * C / CG workgroups are at least half the CUs (below
+    that the row-split passes fill the chip better).  q8 has no say: the fp8 side output
+    stays the same bf16 dx plus its copy."""
+    del q8
+    return (IN_BWD_ONEPASS[0] and in_bwd_onepass_legal(N, HW, C, dts, lds, has_db, has_dy2)
+            and 2 * N * (C // IN_ONEPASS_CG) >= cus)
+
+
+def in_bwd_onepass(dy: Feat, x: Feat, act: int, mr, red, dx: Feat, dy2: Feat = None, q8=None) -> bool:
+    """in_backward in one launch (irgan_in_bwd_onepass[_fp8]): red is an output.  False when
+    the library does not support the arguments -- then NOTHING ran and nothing was written."""
+    N, HW, C = x.N, x.H * x.W, x.C
+    d2 = (dy2.ptr, dy2.dt, dy2.ld, dy2.off) if dy2 is not None else (None, 0, 0, 0)
+    lib = _lib.load()
+    if q8 is not None:
+        y8, qp, ap = q8
+        if not (dy.dt == x.dt == dx.dt == BF16 and (dy2 is None or dy2.dt == BF16)):
+            return False
+        assert y8.dt == FP8 and (y8.N, y8.H, y8.W, y8.C) == (dx.N, dx.H, dx.W, C)
+        rc = lib.irgan_in_bwd_onepass_fp8(dy.ptr, dy.ld, dy.off, d2[0], d2[2], d2[3], x.ptr, x.ld, x.off, act, N, HW,
+                                          C, P(mr), P(red), dx.ptr, dx.ld, dx.off, y8.ptr, y8.ld, y8.off, qp, ap,
+                                          stream())
+    else:
+        rc = lib.irgan_in_bwd_onepass(dy.ptr, dy.dt, dy.ld, dy.off, *d2, x.ptr, x.dt, x.ld, x.off, act, N, HW, C,
+                                      P(mr), P(red), dx.ptr, dx.dt, dx.ld, dx.off, stream())
+    if rc == IRGAN_EUNSUPPORTED:
+        return False
+    if rc != 0:
+        raise _lib.IrganError(f"irgan_in_bwd_onepass failed with code {rc}")
+    return True
+
+
 def in_backward(dy: Feat, x: Feat, act: int, mr, work, red, dx: Feat, db=None, dy2: Feat = None, q8=None):
     """dx = backward of act(IN(x)) applied to (dy [+ dy2]); x = PRE-norm input."""
+    if in_bwd_use_onepass(x.N, x.H * x.W, x.C, (dy.dt, x.dt, dx.dt), (dy.ld, dy.off, x.ld, x.off, dx.ld, dx.off),
+                          _cu_count(x.t.device), db is not None, dy2 is not None, q8):
+        # 6 B per element: the in_bwd_apply roofline line.  The library still refuses where the
+        # reduce pass's row partition does not fit its threads (batches of several hundred
+        # images, C >= 2048): nothing ran, and the three launches below take over
+        if _timed("in_bwd_apply", x, lambda: in_bwd_onepass(dy, x, act, mr, red, dx, q8=q8)):
+            return
     reduce, apply = in_bwd_parts(dy, x, act, mr, work, red, dx, db, dy2, q8)
     _timed("in_bwd_reduce", x, reduce)
     _timed("in_bwd_apply", x, apply)

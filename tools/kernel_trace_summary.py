@@ -5,7 +5,7 @@ for d in sys.argv[1:]:
     for r in rows:
         n=r["Kernel_Name"]
         if "at::native" in n or "copyBuffer" in n or "pack" in n: continue
-        short=n.split("(anonymous namespace)::")[1].split("(")[0]
+        short=(n.split("(anonymous namespace)::")+[n])[1].split("(")[0]   # kernels outside the namespace: the whole name
         g=(r.get("Grid_Size_X"), r.get("Grid_Size_Y"), r.get("Grid_Size_Z"))
         agg[(short,g)].append(int(r["End_Timestamp"])-int(r["Start_Timestamp"]))
     print("==",d)
