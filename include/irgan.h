@@ -197,7 +197,10 @@ IRGAN_API int irgan_weight_pack_batch(const irgan_pack_desc* descs, int32_t n, i
 
 /* ---- InstanceNorm (ir:154-165), per-(n,c) over H*W, eps 1e-5, no affine ---- */
 /* Reductions are two-level and atomic-free: <= IRGAN_IN_PARTS block partials per
- * (n, c) summed in fp64 in a fixed order. */
+ * (n, c) summed in fp64 in a fixed order.
+ * Errors (here and in the BatchNorm section): empty work returns 0; IRGAN_EINVAL, with nothing
+ * launched, for a NULL required pointer, a dtype other than IRGAN_F32 / IRGAN_BF16, act outside
+ * IRGAN_ACT_NONE .. IRGAN_ACT_LRELU, or a slice with off < 0 or off + C > ld. */
 enum { IRGAN_IN_PARTS = 256 };
 /* mr[n][c] = {mean, rstd} from nb float2 (sum, sum of squares) partials per (n, c)
  * written by irgan_conv_fwd_stats (the reduction half of irgan_in_stats). */

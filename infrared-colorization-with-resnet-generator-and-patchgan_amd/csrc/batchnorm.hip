@@ -10,55 +10,12 @@
 // gradients included.  The tables stay per (n, c) (each sample carries its group's entry), so
 // the apply / backward passes and the fused resample consumers index them as InstanceNorm's;
 // the statistics table holds {mean, rstd, mean_lo, 0} (the mean as a two-float sum).
-#include "common.h"
-
-#include <algorithm>
-#include <initializer_list>
+#include "norm_rows.h"
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int V = 8;
 constexpr int BN_PARTS = 128;   // row-pass blocks per image: 128 double2 partials fill the work size
 static_assert(2 * BN_PARTS <= IRGAN_IN_PARTS, "work buffer: IRGAN_IN_PARTS doubles per (n, c)");
-
-template <int VW>
-IRGAN_HD void ldw(const void* p, int dt, long i, float* o) {
-    if constexpr (VW == 8) {
-        if (dt == IRGAN_BF16) {
-            const uint4 u = *(const uint4*)((const bf16_t*)p + i);
-            const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                o[2 * k] = __uint_as_float(w[k] << 16);
-                o[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-            }
-        } else {
-            const float4 a = *(const float4*)((const float*)p + i), b = *(const float4*)((const float*)p + i + 4);
-            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-        }
-    } else {
-        o[0] = ldv(p, dt, i);
-    }
-}
-template <int VW>
-IRGAN_HD void stw(void* p, int dt, long i, const float* v) {
-    if constexpr (VW == 8) {
-        if (dt == IRGAN_BF16) {
-            uint4 u;
-            u.x = pk_bf16(v[0], v[1]);
-            u.y = pk_bf16(v[2], v[3]);
-            u.z = pk_bf16(v[4], v[5]);
-            u.w = pk_bf16(v[6], v[7]);
-            *(uint4*)((bf16_t*)p + i) = u;
-        } else {
-            *(float4*)((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
-            *(float4*)((float*)p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        }
-    } else {
-        stv(p, dt, i, v[0]);
-    }
-}
 
 // the affine output gamma * xhat + beta: ONE expression for the forward and for the backward's
 // activation mask, so both see the same sign
@@ -66,21 +23,6 @@ IRGAN_HD float bn_affine(float xh, float g, float b) { return fmaf(g, xh, b); }
 // xhat from the table entry {mean, rstd, mean_lo}: the mean as a two-float sum, so that its
 // fp32 rounding (half an ulp of |mean|) does not reach xhat when |mean| >> the deviation
 IRGAN_HD float bn_xhat(float x, float mean, float mlo, float rstd) { return ((x - mean) - mlo) * rstd; }
-IRGAN_HD float bn_act(float h, int act) {
-    if (act == IRGAN_ACT_RELU) return h > 0.f ? h : 0.f;
-    if (act == IRGAN_ACT_LRELU) return h > 0.f ? h : 0.2f * h;
-    return h;
-}
-IRGAN_HD float bn_act_grad(float h, int act) {
-    if (act == IRGAN_ACT_RELU) return h > 0.f ? 1.f : 0.f;
-    if (act == IRGAN_ACT_LRELU) return h > 0.f ? 1.f : 0.2f;
-    return 1.f;
-}
-
-struct Slice {
-    const void* p;
-    int dt, ld, off;
-};
 
 // Forward statistics: double2 partials {sum x, sum x^2} per (block, channel), accumulated in
 // fp64 from the first add on (the products of two floats are exact in fp64), so neither a mean
@@ -93,9 +35,14 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(Slice X, int HW, int C, i
     const int n = blockIdx.y;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(HW, r0 + rows_per_block);
+    // Lay's values (norm_rows.h: keep the two spellings equal), written out here and handed to
+    // Lay: computed in Lay's constructor, or in any helper, bn_stats_kernel<8> and
+    // bn_rows_kernel<1, 8> allocate a few registers more and lose a wave of occupancy each
+    // (measured, profiles/norm_rows_refactor.txt; the cause was not looked for further)
     int CL = (C + VW - 1) / VW;
     if (CL > TPB) CL = TPB;
     const int RP = TPB / CL, cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    const Lay L(CL, RP, cl, rl);
     for (int cb = 0; cb < C; cb += CL * VW) {
         const int c = cb + cl * VW;
         const bool on = rl < RP && c < C;   // VW == 8 only with C % 8 == 0: c + 8 <= C
@@ -115,24 +62,11 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(Slice X, int HW, int C, i
                 }
             }
         }
-#pragma unroll
-        for (int k = 0; k < VW; ++k) {
-            s0[threadIdx.x * VW + k] = a0[k];
-            s1[threadIdx.x * VW + k] = a1[k];
-        }
-        __syncthreads();
-        if (on && rl == 0) {   // the first row of lanes sums the RP rows in order
-#pragma unroll
-            for (int k = 0; k < VW; ++k) {
-                double t0 = 0.0, t1 = 0.0;
-                for (int j = 0; j < RP; ++j) {
-                    t0 += s0[(j * CL + cl) * VW + k];
-                    t1 += s1[(j * CL + cl) * VW + k];
-                }
-                part[((long)n * gridDim.x + blockIdx.x) * C + c + k] = make_double2(t0, t1);
-            }
-        }
-        __syncthreads();
+        // ROWS_CHAINS even where the tree would be legal: the order is the result
+        block_reduce<double, VW>(a0, a1, L, ROWS_CHAINS, on, cb, c, C, s0, s1,
+                                 [=](int cc, int k, double t0, double t1) {
+            part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_double2(t0, t1);
+        });
     }
 }
 
@@ -148,9 +82,10 @@ __global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice D
     const int n = blockIdx.y;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(HW, r0 + rows_per_block);
-    int CL = (C + VW - 1) / VW;
+    int CL = (C + VW - 1) / VW;   // Lay's values, written out as in bn_stats_kernel
     if (CL > TPB) CL = TPB;
     const int RP = TPB / CL, cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    const Lay L(CL, RP, cl, rl);
     for (int cb = 0; cb < C; cb += CL * VW) {
         const int c = cb + cl * VW;
         const bool on = rl < RP && c < C;   // VW == 8 only with C % 8 == 0: c + 8 <= C
@@ -182,7 +117,7 @@ __global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice D
 #pragma unroll
                 for (int k = 0; k < VW; ++k) {
                     const float xh = bn_xhat(xv[k], mean[k], mlo[k], rstd[k]);
-                    const float g = gv[k] * bn_act_grad(bn_affine(xh, ga[k], be[k]), act);
+                    const float g = gv[k] * act_grad(bn_affine(xh, ga[k], be[k]), act);
                     if (MODE == 1) { a0[k] += g; a1[k] += g * xh; }
                     else o[k] = ga[k] * rstd[k] * (g - mg[k] - xh * mgx[k]);
                 }
@@ -190,57 +125,30 @@ __global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice D
             }
         }
         if (MODE == 2) continue;   // uniform across the block
-#pragma unroll
-        for (int k = 0; k < VW; ++k) {
-            s0[threadIdx.x * VW + k] = a0[k];
-            s1[threadIdx.x * VW + k] = a1[k];
-        }
-        __syncthreads();
-        if (on && rl == 0) {   // the first row of lanes sums the RP rows in order
-#pragma unroll
-            for (int k = 0; k < VW; ++k) {
-                float t0 = 0.f, t1 = 0.f;
-                for (int j = 0; j < RP; ++j) {
-                    t0 += s0[(j * CL + cl) * VW + k];
-                    t1 += s1[(j * CL + cl) * VW + k];
-                }
-                part[((long)n * gridDim.x + blockIdx.x) * C + c + k] = make_float2(t0, t1);
-            }
-        }
-        __syncthreads();
+        // ROWS_CHAINS even where the tree would be legal: the order is the result
+        block_reduce<float, VW>(a0, a1, L, ROWS_CHAINS, on, cb, c, C, s0, s1,
+                                [=](int cc, int k, float t0, float t1) {
+            part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);
+        });
     }
 }
 
-// fp64 sums of the NG * nb partials of each (group, channel): block = FC channels x FS partial
-// lanes, a lane adds partials sub, sub + FS, ..., then lane 0 of the channel adds the FS lanes
-// in order.  The groups run one after the other (the running buffers take them in order).
-constexpr int FC = 8, FS = 32;
-
+// fp64 sums {s, q} (where sub == 0) of the cnt = NG * nb partials of group grp of a channel, in
+// lane_combine's order.  The groups run one after the other (the running buffers take them in
+// order), so the barrier first: the previous group's reads of sm.
 template <typename P2>
 IRGAN_HD void group_sums(const P2* __restrict__ part, int grp, int cnt, int C, int c, int sub, int cl,
-                         double (*s0)[FC], double (*s1)[FC], double& s, double& q) {
-    s = 0.0;
-    q = 0.0;
-    if (c < C) {
-        const P2* p = part + (long)grp * cnt * C + c;   // images grp*NG .. of nb partials each: contiguous
-        for (int j = sub; j < cnt; j += FS) {
-            const P2 v = p[(long)j * C];
-            s += v.x;
-            q += v.y;
-        }
-    }
-    __syncthreads();   // the previous group's reads of s0 / s1
-    s0[sub][cl] = s;
-    s1[sub][cl] = q;
+                         double (*sm)[FS][FC], double& s, double& q) {
+    const P2* p = part + (long)grp * cnt * C + c;   // images grp*NG .. of nb partials each: contiguous
+    double v[2];
     __syncthreads();
-    if (sub == 0) {
-        s = 0.0;
-        q = 0.0;
-        for (int k = 0; k < FS; ++k) {
-            s += s0[k][cl];
-            q += s1[k][cl];
-        }
-    }
+    lane_combine<2>(cnt, c < C, sub, cl, sm, v, [=](int j, double* t) {
+        const P2 e = p[(long)j * C];
+        t[0] += e.x;
+        t[1] += e.y;
+    });
+    s = v[0];
+    q = v[1];
 }
 
 // forward statistics from {sum x, sum x^2} partials: P2 = double2 (bn_stats_kernel) or float2
@@ -251,7 +159,7 @@ __global__ __launch_bounds__(FC * FS) void bn_finalize_kernel(const P2* __restri
                                                               const float* __restrict__ beta, float* rmean, float* rvar,
                                                               float momentum, float eps, int repeat,
                                                               float* __restrict__ mr, float* __restrict__ ab) {
-    __shared__ double s0[FS][FC], s1[FS][FC];
+    __shared__ double sm[2][FS][FC];
     const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
     const int NG = N / G;
     const bool own = sub == 0 && c < C;
@@ -259,7 +167,7 @@ __global__ __launch_bounds__(FC * FS) void bn_finalize_kernel(const P2* __restri
     if (own && rmean) { rm = rmean[c]; rv = rvar[c]; }
     for (int grp = 0; grp < G; ++grp) {
         double s, q;
-        group_sums(part, grp, NG * nb, C, c, sub, cl, s0, s1, s, q);
+        group_sums(part, grp, NG * nb, C, c, sub, cl, sm, s, q);
         if (!own) continue;
         const double cnt = (double)NG * HW;
         const double mean = s / cnt;
@@ -294,14 +202,14 @@ __global__ __launch_bounds__(FC * FS) void bn_bwd_finalize_kernel(const float2* 
                                                                   int HW, int G, int eval, float* __restrict__ red,
                                                                   float* __restrict__ dgamma,
                                                                   float* __restrict__ dbeta) {
-    __shared__ double s0[FS][FC], s1[FS][FC];
+    __shared__ double sm[2][FS][FC];
     const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
     const int NG = N / G;
     const bool own = sub == 0 && c < C;
     double ts = 0.0, tq = 0.0;
     for (int grp = 0; grp < G; ++grp) {
         double s, q;
-        group_sums(part, grp, NG * nb, C, c, sub, cl, s0, s1, s, q);
+        group_sums(part, grp, NG * nb, C, c, sub, cl, sm, s, q);
         if (!own) continue;
         ts += s;
         tq += q;
@@ -351,7 +259,7 @@ __global__ __launch_bounds__(TPB) void bn_apply_kernel(Slice X, int HW, int C, c
 #pragma unroll
         for (int k = 0; k < VW; ++k) {
             const float4 st = ((const float4*)mr)[(long)n * C + c + k];
-            v[k] = bn_act(bn_affine(bn_xhat(v[k], st.x, st.z, st.y), gamma[c + k], beta[c + k]), act);
+            v[k] = act_fwd(bn_affine(bn_xhat(v[k], st.x, st.z, st.y), gamma[c + k], beta[c + k]), act);
         }
         if (R.p) {
             float rv[VW];
@@ -363,25 +271,8 @@ __global__ __launch_bounds__(TPB) void bn_apply_kernel(Slice X, int HW, int C, c
     }
 }
 
-bool vec_ok(int C, std::initializer_list<int> lds) {
-    if (C % V) return false;
-    for (int l : lds)
-        if (l % V) return false;
-    return true;
-}
-
-// grid of a row pass: >= 8 rows per thread, ~4096 blocks in all, <= BN_PARTS per image
-void rows_grid(int N, int HW, int C, bool vec, int* nb, int* rows) {
-    int cl = vec ? C / V : C;
-    if (cl > TPB) cl = TPB;
-    const int RP = TPB / cl;
-    long b = std::min<long>((4096 + N - 1) / N, irgan_cdiv(HW, 8L * RP));
-    b = std::max<long>(1, std::min<long>(b, BN_PARTS));
-    *rows = irgan_cdiv(HW, b);
-    *nb = irgan_cdiv(HW, *rows);
-}
-
-bool dt_ok(int dt) { return dt == IRGAN_F32 || dt == IRGAN_BF16; }
+// grid of a row pass: >= 8 rows per thread, <= BN_PARTS partials per image
+RowGrid bn_grid(int N, int HW, int C, bool vec) { return row_grid(N, HW, C, vec ? V : 1, 8, BN_PARTS); }
 
 }  // namespace
 
@@ -404,12 +295,12 @@ extern "C" int irgan_bn_stats(const void* x, int32_t dtype, int32_t N, int32_t H
                               float* ab, irgan_stream_t s) {
     if ((long)N * HW * C <= 0) return 0;
     if (!x || !work || !mr || !dt_ok(dtype) || G < 1 || N % G || repeat < 1 || (ab && (!gamma || !beta)) ||
-        (!running_mean != !running_var) || off < 0 || off + C > ld)
+        (!running_mean != !running_var) || !slice_ok(C, ld, off))
         return IRGAN_EINVAL;
     hipStream_t st = (hipStream_t)s;
     const bool vec = vec_ok(C, {ld, off});
-    int nb, rows;
-    rows_grid(N, HW, C, vec, &nb, &rows);
+    const RowGrid rg = bn_grid(N, HW, C, vec);
+    const int nb = rg.nb, rows = rg.rows;
     const Slice X{x, dtype, ld, off};
     const dim3 g(nb, N);   // nb <= BN_PARTS double2 partials per (n, c): 2 * 128 doubles of the work buffer's 256
     if (vec)
@@ -437,8 +328,8 @@ extern "C" int irgan_bn_apply(const void* x, int32_t dtype, int32_t N, int32_t H
                               const float* mr, const float* gamma, const float* beta, int32_t act, const void* res,
                               int32_t ldr, int32_t roff, void* y, int32_t ldy, int32_t yoff, irgan_stream_t s) {
     if ((long)N * HW * C <= 0) return 0;
-    if (!x || !mr || !gamma || !beta || !y || !dt_ok(dtype) || act < IRGAN_ACT_NONE || act > IRGAN_ACT_LRELU ||
-        xoff < 0 || xoff + C > ldx || yoff < 0 || yoff + C > ldy || (res && (roff < 0 || roff + C > ldr)))
+    if (!x || !mr || !gamma || !beta || !y || !dt_ok(dtype) || !act_ok(act) || !slice_ok(C, ldx, xoff) ||
+        !slice_ok(C, ldy, yoff) || (res && !slice_ok(C, ldr, roff)))
         return IRGAN_EINVAL;
     const bool vec = vec_ok(C, {ldx, xoff, ldy, yoff}) && (!res || vec_ok(C, {ldr, roff}));
     const int VW = vec ? V : 1;
@@ -461,14 +352,14 @@ extern "C" int irgan_bn_backward(const void* dy, int32_t dy_dtype, int32_t lddy,
                                  float* dbeta, irgan_stream_t s) {
     if ((long)N * HW * C <= 0) return 0;
     if (!dy || !x || !mr || !gamma || !beta || !work || !red || !dx || !dt_ok(dy_dtype) || !dt_ok(x_dtype) ||
-        !dt_ok(dx_dtype) || (dy2 && !dt_ok(dy2_dtype)) || G < 1 || N % G || act < IRGAN_ACT_NONE ||
-        act > IRGAN_ACT_LRELU || dyoff < 0 || dyoff + C > lddy || xoff < 0 || xoff + C > ldx || dxoff < 0 ||
-        dxoff + C > lddx || (dy2 && (dy2off < 0 || dy2off + C > lddy2)))
+        !dt_ok(dx_dtype) || (dy2 && !dt_ok(dy2_dtype)) || G < 1 || N % G || !act_ok(act) ||
+        !slice_ok(C, lddy, dyoff) || !slice_ok(C, ldx, xoff) || !slice_ok(C, lddx, dxoff) ||
+        (dy2 && !slice_ok(C, lddy2, dy2off)))
         return IRGAN_EINVAL;
     hipStream_t st = (hipStream_t)s;
     const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff, lddx, dxoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
-    int nb, rows;
-    rows_grid(N, HW, C, vec, &nb, &rows);
+    const RowGrid rg = bn_grid(N, HW, C, vec);
+    const int nb = rg.nb, rows = rg.rows;
     const Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
     const dim3 g(nb, N);
     if (vec)

@@ -9,8 +9,10 @@
 // two-level and atomic-free: each block stores one float2 partial per channel
 // (<= IN_PARTS blocks per image), and the finalize launch sums the partials of
 // each (n, c) in fp64, in a fixed order (deterministic), into fp32 (mean, rstd)
-// or (mean g, mean g*xhat).
+// or (mean g, mean g*xhat).  The pieces of a row pass -- the layout, the loads, the grid and
+// the order of every reduction -- are norm_rows.h's, shared with batchnorm.hip.
 #include "fp8_util.h"
+#include "norm_rows.h"
 
 namespace {
 
@@ -24,75 +26,10 @@ struct Q8 {
     uint32_t* amax;
 };
 
-constexpr int TPB = 256;
-constexpr int V = 8;          // channels per thread
 constexpr int IN_PARTS = 128; // max rows-kernel blocks (partials) per image (<= IRGAN_IN_PARTS, the work size)
 
-IRGAN_HD void ld8(const void* p, int dt, long i, float* o) {
-    if (dt == IRGAN_BF16) {
-        const uint4 u = *(const uint4*)((const bf16_t*)p + i);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o[2 * k] = __uint_as_float(w[k] << 16);
-            o[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-        }
-    } else {
-        const float4 a = *(const float4*)((const float*)p + i), b = *(const float4*)((const float*)p + i + 4);
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-    }
-}
-IRGAN_HD void st8(void* p, int dt, long i, const float* v) {
-    if (dt == IRGAN_BF16) {
-        uint4 u;
-        u.x = pk_bf16(v[0], v[1]);
-        u.y = pk_bf16(v[2], v[3]);
-        u.z = pk_bf16(v[4], v[5]);
-        u.w = pk_bf16(v[6], v[7]);
-        *(uint4*)((bf16_t*)p + i) = u;
-    } else {
-        *(float4*)((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
-        *(float4*)((float*)p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    }
-}
-template <int VW>
-IRGAN_HD void ldv_(const void* p, int dt, long i, float* o) {
-    if constexpr (VW == 8) ld8(p, dt, i, o);
-    else o[0] = ldv(p, dt, i);
-}
-template <int VW>
-IRGAN_HD void stv_(void* p, int dt, long i, const float* v) {
-    if constexpr (VW == 8) st8(p, dt, i, v);
-    else stv(p, dt, i, v[0]);
-}
-
-// derivative of the activation that followed the norm, at xhat
-IRGAN_HD float act_grad(float xh, int act) {
-    if (act == IRGAN_ACT_RELU) return xh > 0.f ? 1.f : 0.f;
-    if (act == IRGAN_ACT_LRELU) return xh > 0.f ? 1.f : 0.2f;
-    return 1.f;
-}
-
-struct Slice {
-    const void* p;
-    int dt, ld, off;
-};
-
-// block layout: CL lanes per row (VW channels each), RP rows in parallel
-struct Lay {
-    int CL, RP, cl, rl;
-    __device__ Lay(int C, int VW) {
-        CL = (C + VW - 1) / VW;
-        if (CL > TPB) CL = TPB;
-        RP = TPB / CL;
-        cl = threadIdx.x % CL;
-        rl = threadIdx.x / CL;
-    }
-};
-
 // MODE 0: (sum x, sum x^2); MODE 1: (sum g, sum g*xhat), g = (dy+dy2)*act'(xhat),
-// xhat = (x-mean)*rstd;  MODE 2: MODE-1 pass that also writes dx and sums dx (db);
-// MODE 3: plain channel sum of x into db (bias gradients)
+// xhat = (x-mean)*rstd;  MODE 2: MODE-1 pass that also writes dx and sums dx (db)
 template <int MODE, int VW>
 __global__ __launch_bounds__(TPB) void rows_kernel(Slice X, Slice DY, Slice DY2, int act, const float* __restrict__ mr,
                                                    const float* __restrict__ red, void* __restrict__ dx, int dxdt,
@@ -126,15 +63,15 @@ __global__ __launch_bounds__(TPB) void rows_kernel(Slice X, Slice DY, Slice DY2,
             for (int r = r0 + L.rl; r < r1; r += L.RP) {
                 const long p = (long)n * HW + r;
                 float xv[VW];
-                ldv_<VW>(X.p, X.dt, p * X.ld + X.off + c, xv);
-                if (MODE == 0 || MODE == 3) {
+                ldw<VW>(X.p, X.dt, p * X.ld + X.off + c, xv);
+                if (MODE == 0) {
 #pragma unroll
                     for (int k = 0; k < VW; ++k) { a0[k] += xv[k]; a1[k] += xv[k] * xv[k]; }
                 } else {
                     float gv[VW], g2[VW];
-                    ldv_<VW>(DY.p, DY.dt, p * DY.ld + DY.off + c, gv);
+                    ldw<VW>(DY.p, DY.dt, p * DY.ld + DY.off + c, gv);
                     if (DY2.p) {
-                        ldv_<VW>(DY2.p, DY2.dt, p * DY2.ld + DY2.off + c, g2);
+                        ldw<VW>(DY2.p, DY2.dt, p * DY2.ld + DY2.off + c, g2);
 #pragma unroll
                         for (int k = 0; k < VW; ++k) gv[k] += g2[k];
                     }
@@ -146,135 +83,17 @@ __global__ __launch_bounds__(TPB) void rows_kernel(Slice X, Slice DY, Slice DY2,
                         if (MODE == 1) { a0[k] += g; a1[k] += g * xh; }
                         else { o[k] = rstd[k] * (g - mg[k] - xh * mgx[k]); a0[k] += o[k]; }
                     }
-                    if (MODE == 2) stv_<VW>(dx, dxdt, p * lddx + dxoff + c, o);
+                    if (MODE == 2) stw<VW>(dx, dxdt, p * lddx + dxoff + c, o);
                 }
             }
         }
-        if ((MODE == 2 || MODE == 3) && !db) continue;  // uniform across the block
-        if (L.CL <= 64 && (64 % L.CL) == 0) {
-            // rows of one wave share a lane's channels every CL lanes: butterfly
-            // over them, then one LDS slot per (wave, channel lane)
-            for (int o = L.CL; o < 64; o <<= 1) {
-#pragma unroll
-                for (int k = 0; k < VW; ++k) {
-                    a0[k] += __shfl_xor(a0[k], o, 64);
-                    a1[k] += __shfl_xor(a1[k], o, 64);
-                }
-            }
-            const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-            if (lane < L.CL) {
-#pragma unroll
-                for (int k = 0; k < VW; ++k) {
-                    s0[(wv * L.CL + lane) * VW + k] = a0[k];
-                    s1[(wv * L.CL + lane) * VW + k] = a1[k];
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x < L.CL && cb + threadIdx.x * VW < C) {
-                const int cc = cb + threadIdx.x * VW;
-#pragma unroll
-                for (int k = 0; k < VW; ++k) {
-                    float t0 = 0.f, t1 = 0.f;
-                    for (int j = 0; j < TPB / 64; ++j) {
-                        t0 += s0[(j * L.CL + threadIdx.x) * VW + k];
-                        t1 += s1[(j * L.CL + threadIdx.x) * VW + k];
-                    }
-                    if (MODE == 2 || MODE == 3) atomicAdd(db + cc + k, t0);
-                    else part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);
-                }
-            }
-            __syncthreads();
-            continue;
-        }
-#pragma unroll
-        for (int k = 0; k < VW; ++k) {
-            s0[threadIdx.x * VW + k] = a0[k];
-            s1[threadIdx.x * VW + k] = a1[k];
-        }
-        __syncthreads();
-        // first RP-row of lanes reduces over the RP rows
-        if (on && L.rl == 0) {
-#pragma unroll
-            for (int k = 0; k < VW; ++k) {
-                float t0 = 0.f, t1 = 0.f;
-                for (int j = 0; j < L.RP; ++j) {
-                    t0 += s0[(j * L.CL + L.cl) * VW + k];
-                    t1 += s1[(j * L.CL + L.cl) * VW + k];
-                }
-                if (MODE == 2 || MODE == 3) {
-                    atomicAdd(db + c + k, t0);
-                } else {  // partial of block b of image n: part[(n*nb + b)*C + c]
-                    part[((long)n * gridDim.x + blockIdx.x) * C + c + k] = make_float2(t0, t1);
-                }
-            }
-        }
-        __syncthreads();
+        if (MODE == 2 && !db) continue;  // uniform across the block
+        block_reduce<float, VW>(a0, a1, L, in_row_order(L.CL), on, cb, c, C, s0, s1,
+                                [=](int cc, int k, float t0, float t1) {
+            if (MODE == 2) atomicAdd(db + cc + k, t0);
+            else part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);   // block b of image n
+        });
     }
-}
-
-IRGAN_HD void bf8f(const uint4 u, float* o) {
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        o[2 * k] = __uint_as_float(w[k] << 16);
-        o[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-    }
-}
-
-// Block-wide per-channel sums of (a0, a1) (8 channels per thread) ->
-// part[(n*gridDim.x + blockIdx.x)*C + c]; the same order as rows_kernel's.
-IRGAN_HD void block_partials8(float* a0, float* a1, const Lay& L, bool on, int cb, int c, int C, int n, float* s0,
-                              float* s1, float2* __restrict__ part) {
-    if (L.CL <= 64 && (64 % L.CL) == 0) {
-        for (int o = L.CL; o < 64; o <<= 1) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                a0[k] += __shfl_xor(a0[k], o, 64);
-                a1[k] += __shfl_xor(a1[k], o, 64);
-            }
-        }
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane < L.CL) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                s0[(wv * L.CL + lane) * 8 + k] = a0[k];
-                s1[(wv * L.CL + lane) * 8 + k] = a1[k];
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < L.CL && cb + threadIdx.x * 8 < C) {
-            const int cc = cb + threadIdx.x * 8;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                float t0 = 0.f, t1 = 0.f;
-                for (int j = 0; j < TPB / 64; ++j) {
-                    t0 += s0[(j * L.CL + threadIdx.x) * 8 + k];
-                    t1 += s1[(j * L.CL + threadIdx.x) * 8 + k];
-                }
-                part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);
-            }
-        }
-        __syncthreads();
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        s0[threadIdx.x * 8 + k] = a0[k];
-        s1[threadIdx.x * 8 + k] = a1[k];
-    }
-    __syncthreads();
-    if (on && L.rl == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float t0 = 0.f, t1 = 0.f;
-            for (int j = 0; j < L.RP; ++j) {
-                t0 += s0[(j * L.CL + L.cl) * 8 + k];
-                t1 += s1[(j * L.CL + L.cl) * 8 + k];
-            }
-            part[((long)n * gridDim.x + blockIdx.x) * C + c + k] = make_float2(t0, t1);
-        }
-    }
-    __syncthreads();
 }
 
 // All-bf16 fast path of rows_kernel<MODE, 8> for MODE 0 (stats), 1 (backward
@@ -287,20 +106,17 @@ IRGAN_HD void block_partials8(float* a0, float* a1, const Lay& L, bool on, int c
 // thread walks its rows in batches of U and issues every 16-byte load of a
 // batch, unconverted, before using any; tail rows of the last batch re-load a
 // valid row and are masked.  dx may alias dy (no __restrict__ on either): a
-// thread stores only rows it has already loaded.
-// ROWS8_DB = 1: two register batches in flight (U rows each, the next batch's loads issued
-// before the current one is used); 0 (default): one batch at a time with twice the rows.
-// Measured same box: no faster standalone (tools/norm_bench.py) and -0.5 % on the step
-// (profiles/r05_s5_nab.txt), so the round-4 schedule stays
-#ifndef ROWS8_DB
-#define ROWS8_DB 0
-#endif
+// thread stores only rows it has already loaded.  The loads stay raw uint4 (not ldw, whose
+// conversion would sit between them).
+// One batch at a time: two register batches in flight (U rows each, the next batch's loads
+// issued before the current one is used) measured no faster standalone (tools/norm_bench.py)
+// and -0.5 % on the step on the same box (profiles/r05_s5_nab.txt).
 template <int MODE, int U, bool F8 = false>
 __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, int xoff, const bf16_t* dy, int lddy,
                                                     int dyoff, const bf16_t* dy2, int lddy2, int dy2off, int act,
                                                     const float* __restrict__ mr, const float* __restrict__ red,
                                                     bf16_t* dx, int lddx, int dxoff, int HW, int C, int rows_per_block,
-                                                    float2* __restrict__ part, Q8 q8 = Q8{}) {
+                                                    float2* __restrict__ part, Q8 q8) {
     __shared__ float s0[TPB * 8], s1[TPB * 8];
     const float qs = F8 ? *q8.q : 1.f;
     float amx = 0.f;
@@ -333,41 +149,38 @@ __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, in
             }
         }
         if (on) {
-            // two register batches: batch b + 1's loads are issued before batch b is used, so a
-            // wave keeps a batch in flight while it computes (one batch at a time held the
-            // passes at 2.9-4.8 TB/s, the waves idle between their batches)
-            uint4 xr[2][U], gr[2][U], hr[2][U];
-            auto load = [&](int b, int r) {
+            uint4 xr[U], gr[U], hr[U];
+            auto load = [&](int r) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const long p = pb + min(r + u * L.RP, r1 - 1);
-                    xr[b][u] = *(const uint4*)(x + p * ldx + xoff + c);
-                    if (MODE != 0 && (MODE != 4 || dy)) gr[b][u] = *(const uint4*)(dy + p * lddy + dyoff + c);
+                    xr[u] = *(const uint4*)(x + p * ldx + xoff + c);
+                    if (MODE != 0 && (MODE != 4 || dy)) gr[u] = *(const uint4*)(dy + p * lddy + dyoff + c);
                 }
                 if (MODE != 0 && dy2) {
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         const long p = pb + min(r + u * L.RP, r1 - 1);
-                        hr[b][u] = *(const uint4*)(dy2 + p * lddy2 + dy2off + c);
+                        hr[u] = *(const uint4*)(dy2 + p * lddy2 + dy2off + c);
                     }
                 }
             };
-            auto process = [&](int b, int r) {
+            auto process = [&](int r) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (r + u * L.RP >= r1) break;
                     float xv[8];
-                    bf8f(xr[b][u], xv);
+                    bf8f(xr[u], xv);
                     if (MODE == 0) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k) { a0[k] += xv[k]; a1[k] += xv[k] * xv[k]; }
                         continue;
                     }
                     float gv[8];
-                    if (MODE != 4 || dy) bf8f(gr[b][u], gv);
+                    if (MODE != 4 || dy) bf8f(gr[u], gv);
                     if (dy2) {
                         float hv[8];
-                        bf8f(hr[b][u], hv);
+                        bf8f(hr[u], hv);
 #pragma unroll
                         for (int k = 0; k < 8; ++k) gv[k] += hv[k];
                     }
@@ -375,9 +188,7 @@ __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, in
                     if (MODE == 4) {   // forward apply (as apply_kernel, same float ops)
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
-                            float h = (xv[k] - mean[k]) * rstd[k];
-                            if (act == IRGAN_ACT_RELU) h = h > 0.f ? h : 0.f;
-                            else if (act == IRGAN_ACT_LRELU) h = h > 0.f ? h : 0.2f * h;
+                            const float h = act_fwd((xv[k] - mean[k]) * rstd[k], act);
                             o[k] = dy ? h + gv[k] : h;
                         }
                     } else {
@@ -407,94 +218,80 @@ __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, in
                 }
             };
             const int step = U * L.RP;
-            int r = r0 + L.rl;
-#if ROWS8_DB
-            if (r < r1) load(0, r);
 #pragma unroll 1
-            for (; r < r1; r += 2 * step) {
-                if (r + step < r1) load(1, r + step);
-                process(0, r);
-                if (r + step >= r1) break;
-                if (r + 2 * step < r1) load(0, r + 2 * step);
-                process(1, r + step);
+            for (int r = r0 + L.rl; r < r1; r += step) {
+                load(r);
+                process(r);
             }
-#else
-#pragma unroll 1
-            for (; r < r1; r += step) {
-                load(0, r);
-                process(0, r);
-            }
-#endif
         }
         if (MODE == 2 || MODE == 4) continue;  // uniform across the block
-        block_partials8(a0, a1, L, on, cb, c, C, n, s0, s1, part);
+        block_reduce<float, 8>(a0, a1, L, in_row_order(L.CL), on, cb, c, C, s0, s1,
+                               [=](int cc, int k, float t0, float t1) {
+            part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);
+        });
     }
     if constexpr (F8) fp8_block_amax(amx, q8.amax, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // Rows per thread and rows per load batch (U) of each pass, by key: 0 stats, 1 backward
 // reduce, 2 backward apply, 4 forward apply, 5 forward apply + residual / with the fp8 copy.
-// Measured at the resblock shape, B = 16 (profiles/r05_nsw_norm_sweep.txt, tools/norm_sweep.sh
-// with IRGAN_IN_RPT_M<key> / IRGAN_IN_U_M<key>): forward apply 16.2 -> 14.4 us and backward
+// Measured at the resblock shape, B = 16 (profiles/r05_nsw_norm_sweep.txt, swept through
+// per-pass overrides that have since gone): forward apply 16.2 -> 14.4 us and backward
 // apply 17.9 -> 17.5 at 4 rows per thread in one batch; the reduce stays at 16 rows in batches
 // of 4 (one batch of 4: 20.7 us, 4x the partials), apply + residual at 8 rows in batches of 4
 constexpr int PASS_RPT[6] = {16, 16, 4, 0, 4, 8}, PASS_U[6] = {16, 4, 4, 0, 4, 4};  // U: the batch cap (larger maps: several batches)
-int pass_env(const char* what, int key, int dflt) {
-    char k[32];
-    snprintf(k, sizeof(k), "IRGAN_IN_%s_M%d", what, key);
-    const char* v = getenv(k);
-    return v && atoi(v) > 0 ? atoi(v) : dflt;
-}
-int pass_rpt(int key, int dflt) {
-    static int cache[6] = {0, 0, 0, 0, 0, 0};
-    if (!cache[key]) cache[key] = pass_env("RPT", key, dflt);
-    return cache[key];
-}
-int pass_u(int key) {
-    static int cache[6] = {0, 0, 0, 0, 0, 0};
-    if (!cache[key]) cache[key] = pass_env("U", key, PASS_U[key]);
-    return cache[key];
-}
+
+// What a row pass or the one-pass backward reads and writes, as the entry points fill it;
+// members a pass does not use stay zero.  DY is the residual of the forward apply; q8.p == null:
+// no fp8 copy.
+struct RowArgs {
+    Slice X, DY, DY2;
+    int act;
+    const float *mr, *red;   // red: the row passes read it
+    float* red_out;          // the one-pass backward writes it
+    OSlice DX;
+    int N, HW, C;
+    float2* part;
+    float* db;
+    Q8 q8;
+};
+
+// The kernels keep the parent's loose parameter lists: taking the slices as structs left every
+// register count alone but moved their scalar registers, and two passes then timed beyond the
+// run-to-run spread (profiles/norm_rows_refactor.txt).  These two are the only places that unpack.
+inline const bf16_t* bfp(const Slice& s) { return (const bf16_t*)s.p; }
 
 // rows8_kernel with U = min(the thread's rows, the pass's batch), from the instances 2 / 4 / 8 / 16
-template <int MODE, bool F8 = false, typename... A>
-void rows8_go(int key, int rows_per_thread, dim3 g, hipStream_t st, A... args) {
-    const int u = std::min(pass_u(key), rows_per_thread);
-    if (u <= 2) rows8_kernel<MODE, 2, F8><<<g, TPB, 0, st>>>(args...);
-    else if (u <= 4) rows8_kernel<MODE, 4, F8><<<g, TPB, 0, st>>>(args...);
-    else if (u <= 8) rows8_kernel<MODE, 8, F8><<<g, TPB, 0, st>>>(args...);
-    else rows8_kernel<MODE, 16, F8><<<g, TPB, 0, st>>>(args...);
+template <int MODE, bool F8, int U>
+void rows8_launch(const RowGrid& g, hipStream_t st, const RowArgs& a) {
+    rows8_kernel<MODE, U, F8><<<dim3(g.nb, a.N), TPB, 0, st>>>(
+        bfp(a.X), a.X.ld, a.X.off, bfp(a.DY), a.DY.ld, a.DY.off, bfp(a.DY2), a.DY2.ld, a.DY2.off, a.act, a.mr, a.red,
+        (bf16_t*)a.DX.p, a.DX.ld, a.DX.off, a.HW, a.C, g.rows, a.part, a.q8);
+}
+template <int MODE, bool F8>
+void rows8_go(int key, const RowGrid& g, hipStream_t st, const RowArgs& a) {
+    const int u = std::min(PASS_U[key], irgan_cdiv(g.rows, g.RP));
+    if (u <= 2) rows8_launch<MODE, F8, 2>(g, st, a);
+    else if (u <= 4) rows8_launch<MODE, F8, 4>(g, st, a);
+    else if (u <= 8) rows8_launch<MODE, F8, 8>(g, st, a);
+    else rows8_launch<MODE, F8, 16>(g, st, a);
 }
 
-// fp64 sum of the nb block partials of each (n, c).  Block (FC channels x FS
-// partial lanes) per (image, channel group): a lane adds partials sub, sub + FS,
-// ... (at most nb / FS dependent loads: the launch is latency-bound, so the
-// partial lanes are many and the channel groups narrow), then the FS lanes of a
-// channel combine through LDS in a fixed order (deterministic).
-constexpr int FC = 8, FS = 32;
+// fp64 sum of the nb block partials of each (n, c): one block (FC channels x FS partial
+// lanes) per (image, channel group), the order is lane_combine's (deterministic).
 __global__ __launch_bounds__(256) void finalize_kernel(const float2* __restrict__ part, float* __restrict__ mr, int N,
                                                        int C, int nb, int HW, int mode) {
-    __shared__ double s0[FS][FC], s1[FS][FC];
+    __shared__ double sm[2][FS][FC];
     const int n = blockIdx.y, cl = threadIdx.x % FC, sub = threadIdx.x / FC;
     const int c = blockIdx.x * FC + cl;
-    double s = 0.0, q = 0.0;
-    if (c < C) {
-        for (int b = sub; b < nb; b += FS) {
-            const float2 v = part[((long)n * nb + b) * C + c];
-            s += v.x;
-            q += v.y;
-        }
-    }
-    s0[sub][cl] = s;
-    s1[sub][cl] = q;
-    __syncthreads();
+    double v[2];
+    lane_combine<2>(nb, c < C, sub, cl, sm, v, [&](int b, double* t) {
+        const float2 p = part[((long)n * nb + b) * C + c];
+        t[0] += p.x;
+        t[1] += p.y;
+    });
     if (sub != 0 || c >= C) return;
-    s = 0.0;
-    q = 0.0;
-    for (int k = 0; k < FS; ++k) {
-        s += s0[k][cl];
-        q += s1[k][cl];
-    }
+    const double s = v[0], q = v[1];
     const long i = (long)n * C + c;
     const double mean = s / HW;
     if (mode == 0) {
@@ -508,19 +305,18 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float2* __restrict_
     }
 }
 
-template <int VW, bool F8 = false>
+// forward apply for what rows8_kernel<4> does not take: fp32, scalar channels, an xhat copy
+template <int VW>
 __global__ __launch_bounds__(TPB) void apply_kernel(Slice X, int HW, int C, const float* __restrict__ mr, int act,
                                                     Slice R, void* __restrict__ y, int ldy, int yoff,
-                                                    void* __restrict__ xhat, long total, Q8 q8 = Q8{}) {
+                                                    void* __restrict__ xhat, long total) {
     const int CV = C / VW;
-    const float qs = F8 ? *q8.q : 1.f;
-    float amx = 0.f;
     for (long idx = blockIdx.x * (long)TPB + threadIdx.x; idx < total; idx += (long)gridDim.x * TPB) {
         const long p = idx / CV;
         const int c = (int)(idx - p * CV) * VW;
         const int n = (int)(p / HW);
         float v[VW];
-        ldv_<VW>(X.p, X.dt, p * X.ld + X.off + c, v);
+        ldw<VW>(X.p, X.dt, p * X.ld + X.off + c, v);
         const float4* m4 = (const float4*)(mr + 2 * ((long)n * C + c));
 #pragma unroll
         for (int k = 0; k < VW; k += 2) {
@@ -530,97 +326,53 @@ __global__ __launch_bounds__(TPB) void apply_kernel(Slice X, int HW, int C, cons
             v[k] = (v[k] - st.x) * st.y;
             if (VW > 1) v[k + 1] = (v[k + 1] - st.z) * st.w;
         }
-        if (xhat) stv_<VW>(xhat, X.dt, p * C + c, v);
+        if (xhat) stw<VW>(xhat, X.dt, p * C + c, v);
 #pragma unroll
-        for (int k = 0; k < VW; ++k) {
-            if (act == IRGAN_ACT_RELU) v[k] = v[k] > 0.f ? v[k] : 0.f;
-            else if (act == IRGAN_ACT_LRELU) v[k] = v[k] > 0.f ? v[k] : 0.2f * v[k];
-        }
+        for (int k = 0; k < VW; ++k) v[k] = act_fwd(v[k], act);
         if (R.p) {
             float rv[VW];
-            ldv_<VW>(R.p, R.dt, p * R.ld + R.off + c, rv);
+            ldw<VW>(R.p, R.dt, p * R.ld + R.off + c, rv);
 #pragma unroll
             for (int k = 0; k < VW; ++k) v[k] += rv[k];
         }
-        stv_<VW>(y, X.dt, p * ldy + yoff + c, v);
-        if constexpr (F8) {  // bf16 output, VW == 8
-            float vb[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                vb[k] = bf2f(f2bf(v[k]));
-                amx = fmaxf(amx, fabsf(vb[k]));
-            }
-            *(uint2*)(q8.p + p * q8.ld + q8.off + c) = pack8_fp8(vb, qs);
-        }
+        stw<VW>(y, X.dt, p * ldy + yoff + c, v);
     }
-    if constexpr (F8) fp8_block_amax(amx, q8.amax, blockIdx.x);
 }
 
+// The grid of pass `key` (PASS_RPT): row_grid with <= IN_PARTS partials per image.  rpt 16 for
+// the reductions (stats, backward reduce: half the partials for the finalize), less for the
+// passes that write -- measured per pass at the resblock shape (r03_e: backward reduce +
+// finalize 20.6 -> 17.2 us, apply + ReLU 17.4 -> 16.5, apply + residual 18.1 -> 18.8, backward
+// apply 18.4 -> 18.6; U = 2 / a 128-VGPR cap on the reduce: no gain)
+RowGrid pass_grid(int key, int N, int HW, int C, int VW) { return row_grid(N, HW, C, VW, PASS_RPT[key], IN_PARTS); }
 
-bool vec_ok(int C, std::initializer_list<int> lds) {
-    if (C % V) return false;
-    for (int l : lds)
-        if (l % V) return false;
-    return true;
-}
-
-int rp_of(int C, int VW) {
-    int cl = (C + VW - 1) / VW;
-    if (cl > TPB) cl = TPB;
-    return TPB / cl;
-}
-
-// blocks per image: ~4096 blocks over the grid, >= rpt rows per thread, <= IN_PARTS.
-// rpt 16 for the reductions (stats, backward reduce: half the partials for the finalize)
-// and the plain forward apply, 8 for the three-stream passes (backward apply, apply +
-// residual) -- measured per pass at the resblock shape (tools/norm_sweep.sh, r03_e:
-// backward reduce + finalize 20.6 -> 17.2 us, apply + ReLU 17.4 -> 16.5, apply + residual
-// 18.1 -> 18.8, backward apply 18.4 -> 18.6; U = 2 / a 128-VGPR cap on the reduce: no gain)
-int blocks_per_image(long HW, int N, int RP, long rpt = 8) {
-    long nb = (4096 + N - 1) / (N > 0 ? N : 1);
-    const long maxnb = (HW + rpt * RP - 1) / (rpt * RP);
-    if (nb > maxnb) nb = maxnb;
-    if (nb > IN_PARTS) nb = IN_PARTS;
-    if (nb < 1) nb = 1;
-    return (int)nb;
-}
-
+// Row pass MODE (0 stats, 1 backward reduce, 2 backward apply) over a's slices: rows8_kernel
+// where everything is bf16 in 8-channel vectors and no db is asked for, else rows_kernel.
+// Returns the number of partials per image.
 template <int MODE>
-int launch_rows(Slice X, Slice DY, Slice DY2, int act, const float* mr, const float* red, void* dx, int dxdt, int lddx,
-                int dxoff, int N, int HW, int C, float2* part, float* db, bool vec, hipStream_t st, int* nb_out,
-                const Q8* q8 = nullptr) {
-    const int VW = vec ? V : 1;
-    const int rpt = pass_rpt(MODE, PASS_RPT[MODE]);
-    const int RP = rp_of(C, VW);
-    int nb = blocks_per_image(HW, N, RP, rpt);
-    const int rows = irgan_cdiv(HW, nb);
-    nb = irgan_cdiv(HW, rows);
-    const int rpth = irgan_cdiv(rows, RP);
-    dim3 g(nb, N);
-    static const bool fast = !getenv("IRGAN_NO_ROWS8");
-    const bool bf = X.dt == IRGAN_BF16 && (MODE == 0 || (DY.dt == IRGAN_BF16 && (!DY2.p || DY2.dt == IRGAN_BF16))) &&
-                    (MODE != 2 || (dxdt == IRGAN_BF16 && !db));
-    if (q8 && !(vec && bf && MODE == 2)) return IRGAN_EUNSUPPORTED;
-    if ((fast || q8) && vec && bf && MODE <= 2) {
-        const bf16_t *xp = (const bf16_t*)X.p, *gp = (const bf16_t*)DY.p, *hp = (const bf16_t*)DY2.p;
-        if (MODE == 2 && q8)
-            rows8_go<2, true>(2, rpth, g, st, xp, X.ld, X.off, gp, DY.ld, DY.off, hp, DY2.ld, DY2.off, act, mr, red,
-                              (bf16_t*)dx, lddx, dxoff, HW, C, rows, part, *q8);
-        else if (MODE == 0)
-            rows8_go<0>(0, rpth, g, st, xp, X.ld, X.off, (const bf16_t*)nullptr, 0, 0, (const bf16_t*)nullptr, 0, 0, act, mr,
-                        red, (bf16_t*)nullptr, 0, 0, HW, C, rows, part, Q8{});
-        else
-            rows8_go<MODE>(MODE, rpth, g, st, xp, X.ld, X.off, gp, DY.ld, DY.off, hp, DY2.ld, DY2.off, act, mr, red,
-                           (bf16_t*)dx, lddx, dxoff, HW, C, rows, part, Q8{});
-        if (nb_out) *nb_out = nb;
-        return 0;
+int launch_rows(const RowArgs& a, bool vec, hipStream_t st) {
+    const RowGrid g = pass_grid(MODE, a.N, a.HW, a.C, vec ? V : 1);
+    const bool bf = a.X.dt == IRGAN_BF16 &&
+                    (MODE == 0 || (a.DY.dt == IRGAN_BF16 && (!a.DY2.p || a.DY2.dt == IRGAN_BF16))) &&
+                    (MODE != 2 || (a.DX.dt == IRGAN_BF16 && !a.db));
+    if (vec && bf) {
+        if constexpr (MODE == 2) {   // the one row pass with an fp8 instance (irgan_in_bwd_apply_fp8)
+            if (a.q8.p) {
+                rows8_go<2, true>(2, g, st, a);
+                return g.nb;
+            }
+        }
+        rows8_go<MODE, false>(MODE, g, st, a);
+        return g.nb;
     }
+    const dim3 grid(g.nb, a.N);
     if (vec)
-        rows_kernel<MODE, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, red, dx, dxdt, lddx, dxoff, HW, C, rows, part, db);
+        rows_kernel<MODE, V><<<grid, TPB, 0, st>>>(a.X, a.DY, a.DY2, a.act, a.mr, a.red, a.DX.p, a.DX.dt, a.DX.ld,
+                                                   a.DX.off, a.HW, a.C, g.rows, a.part, a.db);
     else
-        rows_kernel<MODE, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, red, dx, dxdt, lddx, dxoff, HW, C, rows, part, db);
-    if (nb_out) *nb_out = nb;
-    return 0;
+        rows_kernel<MODE, 1><<<grid, TPB, 0, st>>>(a.X, a.DY, a.DY2, a.act, a.mr, a.red, a.DX.p, a.DX.dt, a.DX.ld,
+                                                   a.DX.off, a.HW, a.C, g.rows, a.part, a.db);
+    return g.nb;
 }
 
 // One-pass InstanceNorm backward for maps that fit one CU's registers.  InstanceNorm is
@@ -630,15 +382,19 @@ int launch_rows(Slice X, Slice DY, Slice DY2, int act, const float* mr, const fl
 // the registers it holds -- 6 bytes per element where reduce + finalize + apply move 10, and
 // no partials, finalize launch, ticket or wait on another block.
 // The result is the three launches' bit for bit: the sums are grouped exactly as
-// rows8_kernel<1> + finalize_kernel group them at the same (N, HW, C).  There, block b of nb
-// covers `rows` rows, its thread (rl, channel lane) adds rows r0 + rl, r0 + rl + RP, ... in
-// order (a chain), block_partials8 combines the RP chains of a channel (a butterfly inside
-// each wave then the four waves in order, or the RP chains in order when the channel lanes do
-// not divide a wave), and finalize_kernel adds the nb partials in fp64 (partial b in lane
-// b % FS, the lanes in order).  Here a thread owns one chain of one channel octet (CG / 8
+// rows8_kernel<1> + finalize_kernel group them at the same (N, HW, C), that is, as
+// norm_rows.h's row_grid, block_reduce and lane_combine do.  There, block b of nb covers
+// `rows` rows (row_grid, called through pass_grid by both), its thread (rl, channel lane) adds
+// rows r0 + rl, r0 + rl + RP, ... in order (a chain), block_reduce combines the RP chains of a
+// channel (ROWS_TREE: a butterfly inside each wave then the four waves in order, or
+// ROWS_CHAINS: the RP chains in order, when the channel lanes do not divide a wave), and
+// lane_combine adds the nb partials in fp64 (partial b in lane b % FS, the lanes in order).
+// This kernel cannot call the two: its chains are not laid out as a row pass's block, so it
+// re-enacts both orders in LDS.  Here a thread owns one chain of one channel octet (CG / 8
 // octets): it holds the chain's <= U pixels, sums them in the same order with the same float
-// operations (the fused multiply-adds rows8_kernel compiles to are written out), the chains meet in LDS and are combined in that order, and the fp32 {mean g,
-// mean g*xhat} stored to red are the values dx is computed from.  Tail items re-load a valid
+// operations (the fused multiply-adds rows8_kernel compiles to are written out), the chains
+// meet in LDS and are combined in that order, and the fp32 {mean g, mean g*xhat} stored to red
+// are the values dx is computed from.  Tail items re-load a valid
 // pixel with dy = 0 (they add +-0).  Deterministic; no atomics but the amax record.  The
 // barriers of the reduction sit between a workgroup's last load and its first store and it
 // stores only pixels it loaded, so dx may alias dy.
@@ -736,9 +492,10 @@ __global__ __launch_bounds__(NT) void in_bwd_onepass_kernel(const bf16_t* x, int
         sc[q][(h * 8 + k) * 2 + 1] = a1[k];
     }
     __syncthreads();
-    // block_partials8 of block pbk for one (channel, sum): CL channel lanes of rows8_kernel
+    // block_reduce of block pbk for one (channel, sum), in the order rows8_kernel asks of it
+    // (in_row_order at its CL channel lanes)
     const int CL = min(C / 8, TPB);
-    const bool tree = CL <= 64 && (64 % CL) == 0;
+    const bool tree = in_row_order(CL) == ROWS_TREE;
     for (int task = threadIdx.x; task < nb * CG * 2; task += NT) {
         const int cw = task % (CG * 2), pbk = task / (CG * 2);
         const int c0 = pbk * RP;
@@ -756,7 +513,7 @@ __global__ __launch_bounds__(NT) void in_bwd_onepass_kernel(const bf16_t* x, int
         pt[pbk][cw] = tsum;
     }
     __syncthreads();
-    if (threadIdx.x < CG * 2) {   // finalize_kernel: partial pbk in lane pbk % FS, then the lanes in order
+    if (threadIdx.x < CG * 2) {   // lane_combine: partial pbk in lane pbk % FS, then the lanes in order
         const int cw = threadIdx.x;
         double s = 0.0;
         for (int k = 0; k < FS; ++k) {
@@ -812,20 +569,19 @@ __global__ __launch_bounds__(NT) void in_bwd_onepass_kernel(const bf16_t* x, int
     if constexpr (F8) fp8_block_amax(amx, q8.amax, blockIdx.x);
 }
 
-// The reduce pass's partition at (N, HW, C) (launch_rows<1>): nb blocks of `rows` rows, RP
-// chains each.  False when a chain is longer than OP_MAXU pixels or the chains of the
-// group's octets outnumber OP_MAXNT threads (batches of several hundred images, C >= 2048).
+// The reduce pass's partition at (N, HW, C): the very grid launch_rows<1> launches, nb blocks
+// of `rows` rows, RP chains each.  False when a chain is longer than OP_MAXU pixels or the
+// chains of the group's octets outnumber OP_MAXNT threads (batches of several hundred images,
+// C >= 2048).
 struct OnepassPlan {
-    int nb, rows, RP, chain, threads;
+    RowGrid g;
+    int chain, threads;
 };
 bool onepass_plan(int N, int HW, int C, OnepassPlan* pl) {
-    pl->RP = rp_of(C, 8);
-    int nb = blocks_per_image(HW, N, pl->RP, pass_rpt(1, PASS_RPT[1]));
-    pl->rows = irgan_cdiv(HW, nb);
-    pl->nb = irgan_cdiv(HW, pl->rows);
-    pl->chain = irgan_cdiv(pl->rows, pl->RP);
-    pl->threads = pl->nb * pl->RP * (OP_CG / 8);
-    return pl->chain <= OP_MAXU && pl->threads <= OP_MAXNT && pl->nb <= IN_PARTS;
+    pl->g = pass_grid(1, N, HW, C, V);
+    pl->chain = irgan_cdiv(pl->g.rows, pl->g.RP);
+    pl->threads = pl->g.nb * pl->g.RP * (OP_CG / 8);
+    return pl->chain <= OP_MAXU && pl->threads <= OP_MAXNT && pl->g.nb <= IN_PARTS;
 }
 
 // legal: all-bf16 callers only (the entry points take no dtypes), the slice fits the
@@ -838,43 +594,93 @@ bool onepass_ok(int N, int HW, int C, std::initializer_list<int> lds) {
     return (long)N * HW * C <= 0 || onepass_plan(N, HW, C, &pl);
 }
 
+// the instance with NT >= the plan's threads (128 / 256 / 512) and U >= its chain (1 .. 16)
+template <bool F8, int NT, int U>
+void onepass_launch(const OnepassPlan& pl, hipStream_t st, const RowArgs& a) {
+    in_bwd_onepass_kernel<F8, NT, OP_CG, U><<<a.N * (a.C / OP_CG), NT, 0, st>>>(
+        bfp(a.X), a.X.ld, a.X.off, bfp(a.DY), a.DY.ld, a.DY.off, a.act, a.mr, a.red_out, (bf16_t*)a.DX.p, a.DX.ld,
+        a.DX.off, a.HW, a.C, irgan_xcd_swz(), pl.g.nb, pl.g.rows, pl.g.RP, a.q8);
+}
 template <bool F8, int NT>
-void onepass_nt(const OnepassPlan& pl, dim3 g, hipStream_t st, const bf16_t* x, int ldx, int xoff, const bf16_t* dy,
-                int lddy, int dyoff, int act, const float* mr, float* red, bf16_t* dx, int lddx, int dxoff, int HW,
-                int C, Q8 q8) {
-    const int swz = irgan_xcd_swz();
-#define OP_GO(U_)                                                                                                    \
-    in_bwd_onepass_kernel<F8, NT, OP_CG, U_><<<g, NT, 0, st>>>(x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, \
-                                                                dxoff, HW, C, swz, pl.nb, pl.rows, pl.RP, q8)
-    if (pl.chain <= 1) OP_GO(1);
-    else if (pl.chain <= 2) OP_GO(2);
-    else if (pl.chain <= 4) OP_GO(4);
-    else if (pl.chain <= 8) OP_GO(8);
-    else OP_GO(16);
-#undef OP_GO
+void onepass_nt(const OnepassPlan& pl, hipStream_t st, const RowArgs& a) {
+    if (pl.chain <= 1) onepass_launch<F8, NT, 1>(pl, st, a);
+    else if (pl.chain <= 2) onepass_launch<F8, NT, 2>(pl, st, a);
+    else if (pl.chain <= 4) onepass_launch<F8, NT, 4>(pl, st, a);
+    else if (pl.chain <= 8) onepass_launch<F8, NT, 8>(pl, st, a);
+    else onepass_launch<F8, NT, 16>(pl, st, a);
+}
+template <bool F8>
+void onepass_go(const RowArgs& a, hipStream_t st) {
+    OnepassPlan pl;
+    onepass_plan(a.N, a.HW, a.C, &pl);
+    if (pl.threads <= 128) onepass_nt<F8, 128>(pl, st, a);
+    else if (pl.threads <= 256) onepass_nt<F8, 256>(pl, st, a);
+    else onepass_nt<F8, 512>(pl, st, a);
 }
 
-template <bool F8>
-void onepass_go(const bf16_t* x, int ldx, int xoff, const bf16_t* dy, int lddy, int dyoff, int act, const float* mr,
-                float* red, bf16_t* dx, int lddx, int dxoff, int N, int HW, int C, hipStream_t st, Q8 q8) {
-    OnepassPlan pl;
-    onepass_plan(N, HW, C, &pl);
-    const dim3 g(N * (C / OP_CG));
-    if (pl.threads <= 128) onepass_nt<F8, 128>(pl, g, st, x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, dxoff, HW, C, q8);
-    else if (pl.threads <= 256) onepass_nt<F8, 256>(pl, g, st, x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, dxoff, HW, C, q8);
-    else onepass_nt<F8, 512>(pl, g, st, x, ldx, xoff, dy, lddy, dyoff, act, mr, red, dx, lddx, dxoff, HW, C, q8);
+// the forward apply as rows8_kernel<4> (all bf16, 8-channel vectors, no xhat; the residual in
+// a.DY), grid as the other row passes; a.q8.p: also the fp8 copy of y (irgan_in_apply_fp8)
+void apply_rows(const RowArgs& a, hipStream_t st) {
+    const int key = a.DY.p || a.q8.p ? 5 : 4;  // 5: apply + residual, or with the fp8 copy
+    const RowGrid g = pass_grid(key, a.N, a.HW, a.C, V);
+    if (a.q8.p) rows8_go<4, true>(key, g, st, a);
+    else rows8_go<4, false>(key, g, st, a);
+}
+
+// db[c] += sum of the nb partials' .x, in lane_combine's order (deterministic)
+__global__ __launch_bounds__(256) void colsum_finalize_kernel(const float2* __restrict__ part, float* __restrict__ db,
+                                                              int nb, int C) {
+    __shared__ double sm[1][FS][FC];
+    const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
+    double t[1];
+    lane_combine<1>(nb, c < C, sub, cl, sm, t, [&](int b, double* v) { v[0] += part[(long)b * C + c].x; });
+    if (sub != 0 || c >= C) return;
+    db[c] += (float)t[0];
+}
+
+// the arguments the backward entry points share; false: IRGAN_EINVAL
+bool bwd_args(RowArgs* a, const void* dy, int dy_dtype, int lddy, int dyoff, const void* dy2, int dy2_dtype,
+              int lddy2, int dy2off, const void* x, int x_dtype, int ldx, int xoff, int act, int N, int HW, int C,
+              const float* mr) {
+    if (!dy || !x || !mr || !dt_ok(dy_dtype) || !dt_ok(x_dtype) || (dy2 && !dt_ok(dy2_dtype)) || !act_ok(act) ||
+        !slice_ok(C, lddy, dyoff) || !slice_ok(C, ldx, xoff) || (dy2 && !slice_ok(C, lddy2, dy2off)))
+        return false;
+    a->X = {x, x_dtype, ldx, xoff};
+    a->DY = {dy, dy_dtype, lddy, dyoff};
+    a->DY2 = {dy2, dy2_dtype, lddy2, dy2off};
+    a->act = act; a->mr = mr;
+    a->N = N; a->HW = HW; a->C = C;
+    return true;
+}
+
+// the slices of an all-bf16 backward (the one-pass and fp8 entry points take no dtypes)
+RowArgs bf16_bwd(const void* dy, int lddy, int dyoff, const void* x, int ldx, int xoff, int act, int N, int HW, int C,
+                 const float* mr, void* dx, int lddx, int dxoff) {
+    RowArgs a{};
+    a.X = {x, IRGAN_BF16, ldx, xoff};
+    a.DY = {dy, IRGAN_BF16, lddy, dyoff};
+    a.act = act; a.mr = mr;
+    a.DX = {dx, IRGAN_BF16, lddx, dxoff};
+    a.N = N; a.HW = HW; a.C = C;
+    return a;
 }
 
 }  // namespace
+
+// Argument checks of the entry points (as batchnorm.hip's): empty work returns 0 before them;
+// a null required pointer, an unknown dtype or activation, or a slice that leaves its rows is
+// IRGAN_EINVAL and launches nothing.
 
 extern "C" int irgan_in_stats(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ld,
                               int32_t off, double* work, float* mr, irgan_stream_t s) {
     hipStream_t st = (hipStream_t)s;
     if ((long)N * HW * C <= 0) return 0;
-    Slice X{x, dtype, ld, off}, Z{nullptr, 0, 0, 0};
-    int nb = 1;
-    launch_rows<0>(X, Z, Z, 0, nullptr, nullptr, nullptr, 0, 0, 0, N, HW, C, (float2*)work, nullptr,
-                   vec_ok(C, {ld, off}), st, &nb);
+    if (!x || !work || !mr || !dt_ok(dtype) || !slice_ok(C, ld, off)) return IRGAN_EINVAL;
+    RowArgs a{};
+    a.X = {x, dtype, ld, off};
+    a.N = N; a.HW = HW; a.C = C;
+    a.part = (float2*)work;
+    const int nb = launch_rows<0>(a, vec_ok(C, {ld, off}), st);
     finalize_kernel<<<dim3(irgan_cdiv(C, FC), N), 256, 0, st>>>((const float2*)work, mr, N, C, nb, HW, 0);
     IRGAN_LAUNCH_CHECK();
     return 0;
@@ -889,46 +695,26 @@ extern "C" int irgan_in_finalize(const void* part, int32_t N, int32_t HW, int32_
     return 0;
 }
 
-
-
-// the forward apply as rows8_kernel<4> (bf16, 8-channel vectors, no xhat), grid as the
-// other row passes; q8: also the fp8 copy of y (irgan_in_apply_fp8)
-bool apply_rows(const void* x, int ldx, int xoff, int N, int HW, int C, const float* mr, int act, const void* res,
-                int ldr, int roff, void* y, int ldy, int yoff, hipStream_t st, const Q8* q8 = nullptr) {
-    static const bool off = getenv("IRGAN_NO_APPLY_ROWS") != nullptr;
-    if (off) return false;
-    const int key = res || q8 ? 5 : 4;  // 5: apply + residual, or with the fp8 copy
-    const int rpt = pass_rpt(key, PASS_RPT[key]);
-    const int RP = rp_of(C, 8);
-    int nb = blocks_per_image(HW, N, RP, rpt);
-    const int rows = irgan_cdiv(HW, nb);
-    nb = irgan_cdiv(HW, rows);
-    const int rpth = irgan_cdiv(rows, RP);
-    dim3 g(nb, N);
-    const bf16_t *xp = (const bf16_t*)x, *rp = (const bf16_t*)res;
-    if (q8)
-        rows8_go<4, true>(key, rpth, g, st, xp, ldx, xoff, rp, ldr, roff, (const bf16_t*)nullptr, 0, 0, act, mr,
-                          (const float*)nullptr, (bf16_t*)y, ldy, yoff, HW, C, rows, (float2*)nullptr, *q8);
-    else
-        rows8_go<4>(key, rpth, g, st, xp, ldx, xoff, rp, ldr, roff, (const bf16_t*)nullptr, 0, 0, act, mr,
-                    (const float*)nullptr, (bf16_t*)y, ldy, yoff, HW, C, rows, (float2*)nullptr, Q8{});
-    return true;
-}
-
 extern "C" int irgan_in_apply(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ldx,
                               int32_t xoff, const float* mr, int32_t act, const void* res, int32_t ldr, int32_t roff,
                               void* y, int32_t ldy, int32_t yoff, void* xhat, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!x || !mr || !y || !dt_ok(dtype) || !act_ok(act) || !slice_ok(C, ldx, xoff) || !slice_ok(C, ldy, yoff) ||
+        (res && !slice_ok(C, ldr, roff)))
+        return IRGAN_EINVAL;
     const bool vec = vec_ok(C, {ldx, xoff, ldy, yoff}) && (!res || vec_ok(C, {ldr, roff}));
-    if (vec && dtype == IRGAN_BF16 && !xhat && (long)N * HW * C > 0 &&
-        apply_rows(x, ldx, xoff, N, HW, C, mr, act, res, ldr, roff, y, ldy, yoff, (hipStream_t)s)) {
+    const Slice X{x, dtype, ldx, xoff}, R{res, dtype, ldr, roff};
+    if (vec && dtype == IRGAN_BF16 && !xhat) {
+        RowArgs a{};
+        a.X = X; a.DY = R; a.act = act; a.mr = mr;
+        a.DX = {y, dtype, ldy, yoff};
+        a.N = N; a.HW = HW; a.C = C;
+        apply_rows(a, (hipStream_t)s);
         IRGAN_LAUNCH_CHECK();
         return 0;
     }
-    const int VW = vec ? V : 1;
-    long total = (long)N * HW * (C / VW);
-    if (total <= 0) return 0;
-    int blocks = (int)std::min<long>((total + TPB - 1) / TPB, 16384);
-    Slice X{x, dtype, ldx, xoff}, R{res, dtype, ldr, roff};
+    const long total = (long)N * HW * (C / (vec ? V : 1));
+    const int blocks = (int)std::min<long>((total + TPB - 1) / TPB, 16384);
     if (vec)
         apply_kernel<V><<<blocks, TPB, 0, (hipStream_t)s>>>(X, HW, C, mr, act, R, y, ldy, yoff, xhat, total);
     else
@@ -943,10 +729,14 @@ extern "C" int irgan_in_bwd_reduce(const void* dy, int32_t dy_dtype, int32_t ldd
                                    const float* mr, double* work, float* red, irgan_stream_t s) {
     hipStream_t st = (hipStream_t)s;
     if ((long)N * HW * C <= 0) return 0;
+    RowArgs a{};
+    if (!work || !red ||
+        !bwd_args(&a, dy, dy_dtype, lddy, dyoff, dy2, dy2_dtype, lddy2, dy2off, x, x_dtype, ldx, xoff, act, N, HW, C,
+                  mr))
+        return IRGAN_EINVAL;
+    a.part = (float2*)work;
     const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
-    Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
-    int nb = 1;
-    launch_rows<1>(X, DY, DY2, act, mr, nullptr, nullptr, 0, 0, 0, N, HW, C, (float2*)work, nullptr, vec, st, &nb);
+    const int nb = launch_rows<1>(a, vec, st);
     finalize_kernel<<<dim3(irgan_cdiv(C, FC), N), 256, 0, st>>>((const float2*)work, red, N, C, nb, HW, 1);
     IRGAN_LAUNCH_CHECK();
     return 0;
@@ -957,10 +747,17 @@ extern "C" int irgan_in_bwd_apply(const void* dy, int32_t dy_dtype, int32_t lddy
                                   int32_t ldx, int32_t xoff, int32_t act, int32_t N, int32_t HW, int32_t C,
                                   const float* mr, const float* red, void* dx, int32_t dx_dtype, int32_t lddx,
                                   int32_t dxoff, float* db, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    RowArgs a{};
+    if (!red || !dx || !dt_ok(dx_dtype) || !slice_ok(C, lddx, dxoff) ||
+        !bwd_args(&a, dy, dy_dtype, lddy, dyoff, dy2, dy2_dtype, lddy2, dy2off, x, x_dtype, ldx, xoff, act, N, HW, C,
+                  mr))
+        return IRGAN_EINVAL;
+    a.red = red;
+    a.DX = {dx, dx_dtype, lddx, dxoff};
+    a.db = db;
     const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff, lddx, dxoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
-    Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
-    launch_rows<2>(X, DY, DY2, act, mr, red, dx, dx_dtype, lddx, dxoff, N, HW, C, nullptr, db, vec, (hipStream_t)s,
-                   nullptr);
+    launch_rows<2>(a, vec, (hipStream_t)s);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }
@@ -976,8 +773,9 @@ extern "C" int irgan_in_bwd_onepass(const void* dy, int32_t dy_dtype, int32_t ld
         !onepass_ok(N, HW, C, {lddy, dyoff, ldx, xoff, lddx, dxoff}))
         return IRGAN_EUNSUPPORTED;
     if ((long)N * HW * C <= 0) return 0;
-    onepass_go<false>((const bf16_t*)x, ldx, xoff, (const bf16_t*)dy, lddy, dyoff, act, mr, red, (bf16_t*)dx, lddx,
-                      dxoff, N, HW, C, (hipStream_t)s, Q8{});
+    RowArgs a = bf16_bwd(dy, lddy, dyoff, x, ldx, xoff, act, N, HW, C, mr, dx, lddx, dxoff);
+    a.red_out = red;
+    onepass_go<false>(a, (hipStream_t)s);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }
@@ -991,27 +789,12 @@ extern "C" int irgan_in_bwd_onepass_fp8(const void* dy, int32_t lddy, int32_t dy
     if (!dy || !x || !mr || !red || !dx || !y8 || !q || !amax) return IRGAN_EINVAL;
     if (dy2 || !onepass_ok(N, HW, C, {lddy, dyoff, ldx, xoff, lddx, dxoff, ld8, off8})) return IRGAN_EUNSUPPORTED;
     if ((long)N * HW * C <= 0) return 0;
-    onepass_go<true>((const bf16_t*)x, ldx, xoff, (const bf16_t*)dy, lddy, dyoff, act, mr, red, (bf16_t*)dx, lddx,
-                     dxoff, N, HW, C, (hipStream_t)s, Q8{(uint8_t*)y8, ld8, off8, q, amax});
+    RowArgs a = bf16_bwd(dy, lddy, dyoff, x, ldx, xoff, act, N, HW, C, mr, dx, lddx, dxoff);
+    a.red_out = red;
+    a.q8 = {(uint8_t*)y8, ld8, off8, q, amax};
+    onepass_go<true>(a, (hipStream_t)s);
     IRGAN_LAUNCH_CHECK();
     return 0;
-}
-
-// db[c] += sum of the nb partials' .x: FC channels x FS partial lanes per block (lane k adds
-// partials k, k + FS, ...), then the FS lanes of a channel in order (deterministic)
-static __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float2* __restrict__ part, float* __restrict__ db,
-                                                              int nb, int C) {
-    __shared__ double sp[FS][FC];
-    const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
-    double t = 0.0;
-    if (c < C)
-        for (int b = sub; b < nb; b += FS) t += part[(long)b * C + c].x;
-    sp[sub][cl] = t;
-    __syncthreads();
-    if (sub != 0 || c >= C) return;
-    t = 0.0;
-    for (int k = 0; k < FS; ++k) t += sp[k][cl];
-    db[c] += (float)t;
 }
 
 // Bias gradient (sum over the P rows of each channel).  The rows are split into S <= 16
@@ -1020,14 +803,16 @@ static __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float
 // ~1.6 TB/s), then summed in a fixed order (no atomics).  work: 16 * IN_PARTS * C doubles.
 extern "C" int irgan_channel_sum(const void* g, int32_t dtype, int32_t P, int32_t C, int32_t ld, int32_t off,
                                  float* db, double* work, irgan_stream_t s) {
-    if (P <= 0) return 0;
+    if (P <= 0 || C <= 0) return 0;
+    if (!g || !db || !work || !dt_ok(dtype) || !slice_ok(C, ld, off)) return IRGAN_EINVAL;
     hipStream_t st = (hipStream_t)s;
-    Slice X{g, dtype, ld, off}, Z{nullptr, 0, 0, 0};
     int S = 16;
     while (S > 1 && (P % S || P / S < 4096)) S >>= 1;
-    int nb = 1;
-    launch_rows<0>(X, Z, Z, 0, nullptr, nullptr, nullptr, 0, 0, 0, S, P / S, C, (float2*)work, nullptr,
-                   vec_ok(C, {ld, off}), st, &nb);
+    RowArgs a{};
+    a.X = {g, dtype, ld, off};
+    a.N = S; a.HW = P / S; a.C = C;
+    a.part = (float2*)work;
+    const int nb = launch_rows<0>(a, vec_ok(C, {ld, off}), st);
     colsum_finalize_kernel<<<irgan_cdiv(C, FC), 256, 0, st>>>((const float2*)work, db, S * nb, C);
     IRGAN_LAUNCH_CHECK();
     return 0;
@@ -1041,17 +826,15 @@ extern "C" int irgan_in_apply_fp8(const void* x, int32_t N, int32_t HW, int32_t 
                                   uint32_t* amax, irgan_stream_t s) {
     if (!x || !mr || !y || !y8 || !q || !amax) return IRGAN_EINVAL;
     if (!vec_ok(C, {ldx, xoff, ldy, yoff, ld8, off8}) || (res && !vec_ok(C, {ldr, roff}))) return IRGAN_EUNSUPPORTED;
-    const long total = (long)N * HW * (C / V);
-    if (total <= 0) return 0;
-    const Q8 q8v{(uint8_t*)y8, ld8, off8, q, amax};
-    if (apply_rows(x, ldx, xoff, N, HW, C, mr, act, res, ldr, roff, y, ldy, yoff, (hipStream_t)s, &q8v)) {
-        IRGAN_LAUNCH_CHECK();
-        return 0;
-    }
-    const int blocks = (int)std::min<long>((total + TPB - 1) / TPB, 16384);
-    Slice X{x, IRGAN_BF16, ldx, xoff}, R{res, IRGAN_BF16, ldr, roff};
-    apply_kernel<V, true><<<blocks, TPB, 0, (hipStream_t)s>>>(X, HW, C, mr, act, R, y, ldy, yoff, nullptr, total,
-                                                               q8v);
+    if ((long)N * HW * C <= 0) return 0;
+    RowArgs a{};
+    a.X = {x, IRGAN_BF16, ldx, xoff};
+    a.DY = {res, IRGAN_BF16, ldr, roff};
+    a.act = act; a.mr = mr;
+    a.DX = {y, IRGAN_BF16, ldy, yoff};
+    a.N = N; a.HW = HW; a.C = C;
+    a.q8 = {(uint8_t*)y8, ld8, off8, q, amax};
+    apply_rows(a, (hipStream_t)s);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }
@@ -1063,13 +846,15 @@ extern "C" int irgan_in_bwd_apply_fp8(const void* dy, int32_t lddy, int32_t dyof
                                       uint32_t* amax, irgan_stream_t s) {
     if (!dy || !x || !mr || !red || !dx || !y8 || !q || !amax) return IRGAN_EINVAL;
     if ((long)N * HW * C <= 0) return 0;
-    const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff, lddx, dxoff, ld8, off8}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
+    // all bf16 in 8-channel vectors and no db: what launch_rows<2> needs to take rows8_kernel's fp8 instance
+    const bool vec =
+        vec_ok(C, {lddy, dyoff, ldx, xoff, lddx, dxoff, ld8, off8}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
     if (!vec) return IRGAN_EUNSUPPORTED;
-    Slice X{x, IRGAN_BF16, ldx, xoff}, DY{dy, IRGAN_BF16, lddy, dyoff}, DY2{dy2, IRGAN_BF16, lddy2, dy2off};
-    const Q8 q8{(uint8_t*)y8, ld8, off8, q, amax};
-    const int rc = launch_rows<2>(X, DY, DY2, act, mr, red, dx, IRGAN_BF16, lddx, dxoff, N, HW, C, nullptr, nullptr,
-                                  true, (hipStream_t)s, nullptr, &q8);
-    if (rc) return rc;
+    RowArgs a = bf16_bwd(dy, lddy, dyoff, x, ldx, xoff, act, N, HW, C, mr, dx, lddx, dxoff);
+    a.red = red;
+    a.DY2 = {dy2, IRGAN_BF16, lddy2, dy2off};
+    a.q8 = {(uint8_t*)y8, ld8, off8, q, amax};
+    launch_rows<2>(a, true, (hipStream_t)s);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -326,13 +326,27 @@ class INLayer:
     fused_resample = True
     sum_bias_grad = False
 
+    @staticmethod
+    def _work(bufs: Buffers, N, C):
+        """The norm kernels' shared fp64 scratch: ops.IN_PARTS doubles per (n, c)."""
+        return bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
+
+    @staticmethod
+    def _red(bufs: Buffers, N, C):
+        """The backward's {mean g, mean g*xhat} per (n, c)."""
+        return bufs.flat("in_red", 2 * N * C)
+
+    @staticmethod
+    def _no_fp8():
+        raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+
     def fwd(self, bufs: Buffers, name: str, x: Feat, y: Feat, act, res: Feat = None, xhat=None, nb=0, q8=None):
         """nb > 0: x's statistics partials are already in the shared work buffer
         (written by the producing conv, conv_fwd); only the reduction runs.
         The {mean, rstd} table stays in ``bufs`` under ``name`` for bwd().
         q8: also write y's fp8 copy (ops.in_apply)."""
         N, C = x.N, x.C
-        work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
+        work = self._work(bufs, N, C)
         mr = bufs.get("mr_" + name, (N * C * 2,), torch.float32)
         if nb:
             ops.in_finalize(x, work, nb, mr)
@@ -343,14 +357,14 @@ class INLayer:
     def conv_fwd8(self, bufs: Buffers, name: str, pc, w8, dqw, x8: Feat, dqx, z: Feat, y: Feat, act,
                   res: Feat = None, q8=None):
         """conv_fwd on fp8 operands (ops.conv_fwd_fp8) with the fused statistics."""
-        work = bufs.flat("in_work", ops.IN_PARTS * z.N * z.C, torch.float64)
+        work = self._work(bufs, z.N, z.C)
         nb = ops.conv_fwd_fp8(pc, w8, dqw, x8, dqx, z, part=work)
         self.fwd(bufs, name, z, y, act, res=res, nb=nb, q8=q8)
 
     def conv_fwd(self, bufs: Buffers, name: str, pc, x: Feat, z: Feat, y: Feat, act, res: Feat = None):
         """z = conv(x) (kept for the backward), y = act(IN(z) [+ res]): the IN statistics
         come from the conv's epilogue when it has a fused kernel (ops.conv_fwd_stats)."""
-        work = bufs.flat("in_work", ops.IN_PARTS * z.N * z.C, torch.float64)
+        work = self._work(bufs, z.N, z.C)
         nb = ops.conv_fwd_stats(pc, x, z, work) if INLayer.fused_stats else 0
         if not nb:
             ops.conv_fwd(pc, x, z)
@@ -360,7 +374,7 @@ class INLayer:
         """z = conv(x) and z's {mean, rstd} table (returned, kept for bwd()) -- no apply:
         the consumer normalises on load (ops.blur_down_in / ops.upsample_in).
         conv8 = (w8, dqw, x8, dqx): the conv on fp8 operands (ops.conv_fwd_fp8)."""
-        work = bufs.flat("in_work", ops.IN_PARTS * z.N * z.C, torch.float64)
+        work = self._work(bufs, z.N, z.C)
         mr = bufs.get("mr_" + name, (z.N * z.C * 2,), torch.float32)
         if conv8 is not None:
             w8, dqw, x8, dqx = conv8
@@ -394,8 +408,8 @@ class INLayer:
         q8: also write dx's fp8 copy (ops.in_backward).  wgrad: accumulate the norm's own
         parameter gradients (BNLayer; InstanceNorm has none)."""
         N, C = z.N, z.C
-        work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
-        red = bufs.flat("in_red", 2 * N * C)
+        work = self._work(bufs, N, C)
+        red = self._red(bufs, N, C)
         mr = bufs.d["mr_" + name]
         ops.in_backward(dy, z, act, mr, work, red, dx, db=db if INLayer.sum_bias_grad else None, dy2=dy2,
                         q8=q8 if not INLayer.sum_bias_grad else None)
@@ -417,11 +431,11 @@ class NoNorm(INLayer):
 
     def fwd(self, bufs, name, x, y, act, res=None, xhat=None, nb=0, q8=None):
         if q8 is not None:
-            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+            self._no_fp8()
         ops.in_apply(x, self._ident(bufs, name, x.N, x.C), y, act=act, res=res)
 
     def conv_fwd8(self, *a, **kw):
-        raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+        self._no_fp8()
 
     def conv_fwd(self, bufs, name, pc, x, z, y, act, res=None):
         ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
@@ -429,7 +443,7 @@ class NoNorm(INLayer):
 
     def conv_stats(self, bufs, name, pc, x, z, conv8=None):
         if conv8 is not None:
-            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+            self._no_fp8()
         ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
         return self._ident(bufs, name, z.N, z.C)
 
@@ -480,7 +494,7 @@ class BNLayer(INLayer):
         if not self.training:
             ops.bn_eval_table(self.running_mean, self.running_var, self.gamma, self.beta, N, mr, ab)
             return mr, ab
-        work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
+        work = self._work(bufs, N, C)
         ops.bn_stats(x, work, mr, self.groups, self.gamma, self.beta, self.running_mean, self.running_var, self.repeat,
                      ab=ab, nb=nb)
         self.num_batches_tracked += self.repeat * self.groups
@@ -488,18 +502,18 @@ class BNLayer(INLayer):
 
     def fwd(self, bufs, name, x, y, act, res=None, xhat=None, nb=0, q8=None):
         if q8 is not None or xhat is not None:
-            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+            self._no_fp8()
         mr, _ = self._tables(bufs, name, x, nb)
         ops.bn_apply(x, mr, self.gamma, self.beta, y, act=act, res=res)
 
     def conv_fwd8(self, *a, **kw):
-        raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+        self._no_fp8()
 
     def _conv(self, bufs, pc, x, z):
         """z = conv(x); the partials per image in the work buffer (0: none were written)."""
         nb = 0
         if self.training and INLayer.fused_stats:
-            nb = ops.conv_fwd_stats(pc, x, z, bufs.flat("in_work", ops.IN_PARTS * z.N * z.C, torch.float64))
+            nb = ops.conv_fwd_stats(pc, x, z, self._work(bufs, z.N, z.C))
         if not nb:
             ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
         return nb
@@ -511,12 +525,12 @@ class BNLayer(INLayer):
         """z = conv(x); returns the {shift, scale} table the fused resample consumers read with
         ops.NORM_AFFINE (the {mean, rstd} table stays in ``bufs`` for bwd())."""
         if conv8 is not None:
-            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+            self._no_fp8()
         return self._tables(bufs, name, z, self._conv(bufs, pc, x, z), want_ab=True)[1]
 
     def resample_fwd(self, bufs, name, pc, x, z, a_name, act, y, fused, plain, conv8=None, q8=None):
         if q8 is not None:
-            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+            self._no_fp8()
         ab = self.conv_stats(bufs, name, pc, x, z, conv8=conv8)
         if INLayer.fused_resample and fused(z, ab, act | ops.NORM_AFFINE, y):
             return
@@ -526,11 +540,11 @@ class BNLayer(INLayer):
 
     def bwd(self, bufs, name, dy, z, act, dx, db=None, dy2=None, q8=None, wgrad=True):
         if q8 is not None:
-            raise NotImplementedError("the fp8 path runs with InstanceNorm (norm='instance')")
+            self._no_fp8()
         training, groups = bufs.state["bn_" + name]
         N, C = z.N, z.C
-        work = bufs.flat("in_work", ops.IN_PARTS * N * C, torch.float64)
-        red = bufs.flat("in_red", 2 * N * C)
+        work = self._work(bufs, N, C)
+        red = self._red(bufs, N, C)
         ops.bn_backward(dy, z, act, bufs.d["mr_" + name], self.gamma, self.beta, work, red, dx,
                         dgamma=self.dgamma if wgrad else None, dbeta=self.dbeta if wgrad else None, groups=groups,
                         eval_mode=not training, dy2=dy2)

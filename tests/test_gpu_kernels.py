@@ -147,7 +147,8 @@ def test_channel_sum(ops, P, C, ld):
     assert torch.allclose(db.double(), ref, rtol=1e-5, atol=1e-3)
 
 
-@pytest.mark.parametrize("shape", [(2, 96, 12), (1, 64, 96), (3, 256, 40)])
+# (2, 12, 9), (2, 4, 11): scalar channels (C % 8 != 0), the RP chains in order / the wave tree
+@pytest.mark.parametrize("shape", [(2, 96, 12), (1, 64, 96), (3, 256, 40), (2, 12, 9), (2, 4, 11)])
 @pytest.mark.parametrize("act", [0, 1, 2])
 def test_instance_norm_fwd_bwd(ops, act, shape):
     torch.manual_seed(2)
