@@ -327,6 +327,52 @@ IRGAN_API int irgan_bn_backward(const void* dy, int32_t dy_dtype, int32_t lddy, 
                       float* red, void* dx, int32_t dx_dtype, int32_t lddx, int32_t dxoff, float* dgamma,
                       float* dbeta, irgan_stream_t s);
 
+/* ---- SyncBN: BatchNorm2d (ir:158-159) with nn.SyncBatchNorm's semantics over data-parallel ranks ---- */
+/* The statistics of a group are those of the group's samples on ALL ranks.  Each pass above is
+ * cut in two: a local half that leaves fp64 sums, and a finishing half that reads the sums after
+ * the caller has added the buffers of all ranks (one all-reduce(SUM) per forward and one per
+ * backward; nothing here communicates).  A buffer is G * (2 * C + 1) contiguous doubles:
+ *   sums[G][C] = {sum x, sum x^2}  (backward: {sum g, sum g * xhat}),  then
+ *   cnt[G]     = the group's LOCAL element count N / G * HW.
+ * The count travels with the sums, so the finishing halves divide by the reduced count and never
+ * see the world size: ranks with different N (uneven shards) stay exact.  The local sums are
+ * irgan_bn_stats' / irgan_bn_backward's (fp64, fixed order, no atomics) and the finishing halves
+ * share their arithmetic, so a buffer finished unreduced (one rank) gives the bits of
+ * irgan_bn_stats / irgan_bn_finalize / irgan_bn_backward (for the backward: where dx takes the
+ * same 8-channel / scalar form as dy and x).  Eval mode has no sync form: it reads no batch
+ * statistics (irgan_bn_eval_table, irgan_bn_backward with eval != 0). */
+/* Forward, local half.  nb == 0: a statistics pass over the slice x (as irgan_bn_stats) runs
+ * first; nb > 0: work already holds the nb float2 partials per (n, c) of irgan_conv_fwd_stats
+ * and x is not read (may be NULL).  work: IRGAN_IN_PARTS*N*C doubles. */
+IRGAN_API int irgan_bn_sync_sums(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ld,
+                       int32_t off, int32_t G, int32_t nb, double* work, double* sums, irgan_stream_t s);
+/* Forward, finishing half, from the REDUCED buffer: mr / ab (may be NULL) for the N LOCAL samples
+ * and the running update of irgan_bn_finalize with the global mean and unbiased variance
+ * (n = the reduced count), group after group, each `repeat` times -- nn.SyncBatchNorm's update;
+ * every rank computes it from the same bytes. */
+IRGAN_API int irgan_bn_sync_finalize(const double* sums, int32_t N, int32_t C, int32_t G, const float* gamma,
+                           const float* beta, float* running_mean, float* running_var, float momentum,
+                           float eps, int32_t repeat, float* mr, float* ab, irgan_stream_t s);
+/* Backward, local half: bsums[g][c] = {sum g, sum g * xhat} over the local samples of the group
+ * (g and xhat as irgan_bn_backward) and the counts; dbeta / dgamma += the LOCAL sums over all
+ * groups.  The parameter gradients are NOT part of the buffer: they are averaged over the ranks
+ * with every other gradient, which is what DDP does around nn.SyncBatchNorm. */
+IRGAN_API int irgan_bn_sync_backward_sums(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff,
+                                const void* dy2, int32_t dy2_dtype, int32_t lddy2, int32_t dy2off,
+                                const void* x, int32_t x_dtype, int32_t ldx, int32_t xoff, int32_t act,
+                                int32_t N, int32_t HW, int32_t C, int32_t G, const float* mr,
+                                const float* gamma, const float* beta, double* work, double* bsums,
+                                float* dgamma, float* dbeta, irgan_stream_t s);
+/* Backward, finishing half: dx = gamma * rstd * (g - mean g - xhat * mean(g * xhat)), the two
+ * means = the REDUCED bsums over the reduced count, formed inside the dx pass (one launch, no
+ * table: local half + finishing half are irgan_bn_backward's three launches).  dx may alias dy. */
+IRGAN_API int irgan_bn_sync_backward_dx(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff,
+                              const void* dy2, int32_t dy2_dtype, int32_t lddy2, int32_t dy2off,
+                              const void* x, int32_t x_dtype, int32_t ldx, int32_t xoff, int32_t act,
+                              int32_t N, int32_t HW, int32_t C, int32_t G, const float* mr,
+                              const float* gamma, const float* beta, const double* bsums, void* dx,
+                              int32_t dx_dtype, int32_t lddx, int32_t dxoff, irgan_stream_t s);
+
 /* ---- resampling (ir:269-355 and reflection-pad backward) ---- */
 /* Per-axis tables of a separable resampling map (host only, no GPU work).
  * kind 0: Downsample = reflect pad 1 + [1,2,1]/4 taps, stride 2 (ir:269-310);

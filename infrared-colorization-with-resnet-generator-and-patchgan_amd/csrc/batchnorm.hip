@@ -10,6 +10,13 @@
 // gradients included.  The tables stay per (n, c) (each sample carries its group's entry), so
 // the apply / backward passes and the fused resample consumers index them as InstanceNorm's;
 // the statistics table holds {mean, rstd, mean_lo, 0} (the mean as a two-float sum).
+//
+// SyncBN (nn.SyncBatchNorm's semantics over data-parallel ranks): the same passes cut between
+// "sum locally" and "finish from sums".  The local halves leave the fp64 group sums and the
+// group's local element count in one buffer (sums[G][C][2], cnt[G]: include/irgan.h), the
+// caller adds the buffers of all ranks, and the finishing halves run bn_group_finish / the
+// backward means on the reduced values -- the arithmetic of the local kernels, so one rank's
+// sums finished give the local path's bits.
 #include "norm_rows.h"
 
 namespace {
@@ -70,14 +77,19 @@ __global__ __launch_bounds__(TPB) void bn_stats_kernel(Slice X, int HW, int C, i
     }
 }
 
-// MODE 1: float2 partials {sum g, sum g * xhat}; MODE 2: dx (no partials).
+// MODE 1: float2 partials {sum g, sum g * xhat}; MODE 2: dx (no partials), the means from the
+// red table; MODE 3 (SyncBN): dx, the means formed here from the REDUCED fp64 sums -- `red` then
+// points at a sync buffer (sums[G][C] double2, cnt[G]), NG = samples per group.  The two fp64
+// divisions per channel are bn_bwd_finalize_kernel's expressions (one rank: its bits); they cost
+// bn_rows_kernel<3, 8> 2 VGPRs over <2, 8> (140 / 138, the same waves per SIMD) and leave the
+// other instantiations' allocation as it was.
 // Block: CL lanes across the channels (VW each), RP rows in parallel; grid (blocks per image, N).
 template <int MODE, int VW>
 __global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice DY2, int act,
                                                       const float* __restrict__ mr, const float* __restrict__ red,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       void* dx, int dxdt, int lddx, int dxoff, int HW, int C,
-                                                      int rows_per_block, float2* __restrict__ part) {
+                                                      int rows_per_block, float2* __restrict__ part, int NG) {
     __shared__ float s0[TPB * VW], s1[TPB * VW];
     const int n = blockIdx.y;
     const int r0 = blockIdx.x * rows_per_block;
@@ -101,6 +113,12 @@ __global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice D
                     const float2 rd = ((const float2*)red)[(long)n * C + c + k];
                     mg[k] = rd.x; mgx[k] = rd.y;
                 }
+                if (MODE == 3) {
+                    const int grp = n / NG, G = gridDim.y / NG;
+                    const double cnt = ((const double*)red)[2L * G * C + grp];
+                    const double2 e = ((const double2*)red)[(long)grp * C + c + k];
+                    mg[k] = (float)(e.x / cnt); mgx[k] = (float)(e.y / cnt);
+                }
             }
 #pragma unroll 4
             for (int r = r0 + rl; r < r1; r += RP) {
@@ -121,10 +139,10 @@ __global__ __launch_bounds__(TPB) void bn_rows_kernel(Slice X, Slice DY, Slice D
                     if (MODE == 1) { a0[k] += g; a1[k] += g * xh; }
                     else o[k] = ga[k] * rstd[k] * (g - mg[k] - xh * mgx[k]);
                 }
-                if (MODE == 2) stw<VW>(dx, dxdt, p * lddx + dxoff + c, o);
+                if (MODE >= 2) stw<VW>(dx, dxdt, p * lddx + dxoff + c, o);
             }
         }
-        if (MODE == 2) continue;   // uniform across the block
+        if (MODE >= 2) continue;   // uniform across the block
         // ROWS_CHAINS even where the tree would be legal: the order is the result
         block_reduce<float, VW>(a0, a1, L, ROWS_CHAINS, on, cb, c, C, s0, s1,
                                 [=](int cc, int k, float t0, float t1) {
@@ -151,6 +169,49 @@ IRGAN_HD void group_sums(const P2* __restrict__ part, int grp, int cnt, int C, i
     q = v[1];
 }
 
+// One group's statistics of a channel from its fp64 sums {s, q} over cnt elements: the table
+// entry {mean, rstd, mean_lo}, the {shift b, scale a} pair (want_ab) and the unbiased variance
+// the running buffers take.  ONE function for bn_finalize_kernel and bn_sync_finalize_kernel:
+// the local and the synchronised path finish a group with the same operations.
+struct BnGroup {
+    float mean, rstd, mlo, a, b, unb;
+};
+IRGAN_HD BnGroup bn_group_finish(double s, double q, double cnt, float eps, bool want_ab,
+                                 const float* __restrict__ gamma, const float* __restrict__ beta, int c) {
+    BnGroup r;
+    const double mean = s / cnt;
+    double var = q / cnt - mean * mean;
+    if (var < 0) var = 0;
+    const double rstd = 1.0 / sqrt(var + (double)eps);
+    r.mean = (float)mean;
+    r.rstd = (float)rstd;
+    r.mlo = (float)(mean - (double)r.mean);
+    r.a = 0.f;
+    r.b = 0.f;
+    if (want_ab) {   // y = x * a + b, from the ROUNDED table the apply pass uses
+        r.a = gamma[c] * r.rstd;
+        r.b = (float)((double)beta[c] - mean * (double)r.a);
+    }
+    r.unb = (float)(cnt > 1.0 ? var * cnt / (cnt - 1.0) : var);
+    return r;
+}
+// the group's entry into the tables of its samples n0 .. n0 + NG - 1
+IRGAN_HD void bn_group_store(const BnGroup& r, int n0, int NG, int C, int c, float* __restrict__ mr,
+                             float* __restrict__ ab) {
+    for (int i = 0; i < NG; ++i) {
+        const long e = (long)(n0 + i) * C + c;
+        ((float4*)mr)[e] = make_float4(r.mean, r.rstd, r.mlo, 0.f);
+        if (ab) ((float2*)ab)[e] = make_float2(r.b, r.a);
+    }
+}
+// as nn.BatchNorm2d: fp32 buffers, one update per forward
+IRGAN_HD void bn_running_update(float& rm, float& rv, float momentum, const BnGroup& r, int repeat) {
+    for (int i = 0; i < repeat; ++i) {
+        rm = (1.f - momentum) * rm + momentum * r.mean;
+        rv = (1.f - momentum) * rv + momentum * r.unb;
+    }
+}
+
 // forward statistics from {sum x, sum x^2} partials: P2 = double2 (bn_stats_kernel) or float2
 // (irgan_conv_fwd_stats)
 template <typename P2>
@@ -169,31 +230,61 @@ __global__ __launch_bounds__(FC * FS) void bn_finalize_kernel(const P2* __restri
         double s, q;
         group_sums(part, grp, NG * nb, C, c, sub, cl, sm, s, q);
         if (!own) continue;
-        const double cnt = (double)NG * HW;
-        const double mean = s / cnt;
-        double var = q / cnt - mean * mean;
-        if (var < 0) var = 0;
-        const double rstd = 1.0 / sqrt(var + (double)eps);
-        const float meanf = (float)mean, rstdf = (float)rstd, mlof = (float)(mean - (double)meanf);
-        float a = 0.f, b = 0.f;
-        if (ab) {   // y = x * a + b, from the ROUNDED table the apply pass uses
-            a = gamma[c] * rstdf;
-            b = (float)((double)beta[c] - mean * (double)a);
-        }
-        for (int i = 0; i < NG; ++i) {
-            const long e = (long)(grp * NG + i) * C + c;
-            ((float4*)mr)[e] = make_float4(meanf, rstdf, mlof, 0.f);
-            if (ab) ((float2*)ab)[e] = make_float2(b, a);
-        }
-        if (rmean) {
-            const float unb = (float)(cnt > 1.0 ? var * cnt / (cnt - 1.0) : var);
-            for (int r = 0; r < repeat; ++r) {   // as nn.BatchNorm2d: fp32 buffers, one update per forward
-                rm = (1.f - momentum) * rm + momentum * meanf;
-                rv = (1.f - momentum) * rv + momentum * unb;
-            }
-        }
+        const BnGroup r = bn_group_finish(s, q, (double)NG * HW, eps, ab != nullptr, gamma, beta, c);
+        bn_group_store(r, grp * NG, NG, C, c, mr, ab);
+        if (rmean) bn_running_update(rm, rv, momentum, r, repeat);
     }
     if (own && rmean) { rmean[c] = rm; rvar[c] = rv; }
+}
+
+// ---- SyncBN halves.  Buffer of a layer: sums[G][C] double2, then cnt[G] (G * (2C + 1) doubles).
+
+// Local half of the forward (P2 = double2 / float2 as bn_finalize_kernel: {sum x, sum x^2}) and
+// of the backward (float2 {sum g, sum g * xhat}; dbeta / dgamma += the LOCAL sums over all groups,
+// as bn_bwd_finalize_kernel): the group sums in group_sums' order and the local element count.
+template <typename P2>
+__global__ __launch_bounds__(FC * FS) void bn_sync_sums_kernel(const P2* __restrict__ part, int N, int C, int nb,
+                                                               int HW, int G, double* __restrict__ out,
+                                                               float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    __shared__ double sm[2][FS][FC];
+    const int cl = threadIdx.x % FC, sub = threadIdx.x / FC, c = blockIdx.x * FC + cl;
+    const int NG = N / G;
+    const bool own = sub == 0 && c < C;
+    double ts = 0.0, tq = 0.0;
+    for (int grp = 0; grp < G; ++grp) {
+        double s, q;
+        group_sums(part, grp, NG * nb, C, c, sub, cl, sm, s, q);
+        if (!own) continue;
+        ts += s;
+        tq += q;
+        ((double2*)out)[(long)grp * C + c] = make_double2(s, q);
+        if (c == 0) out[2L * G * C + grp] = (double)NG * HW;
+    }
+    if (own) {
+        if (dbeta) dbeta[c] += (float)ts;
+        if (dgamma) dgamma[c] += (float)tq;
+    }
+}
+
+// Finishing half of the forward: a thread per channel, the groups in order, from the REDUCED
+// buffer (the count is the reduced one: no world size, uneven shards stay right).
+__global__ __launch_bounds__(64) void bn_sync_finalize_kernel(const double* __restrict__ sums, int N, int C, int G,
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float* rmean, float* rvar,
+                                                              float momentum, float eps, int repeat,
+                                                              float* __restrict__ mr, float* __restrict__ ab) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    const int NG = N / G;
+    float rm = 0.f, rv = 0.f;
+    if (rmean) { rm = rmean[c]; rv = rvar[c]; }
+    for (int grp = 0; grp < G; ++grp) {
+        const double2 e = ((const double2*)sums)[(long)grp * C + c];
+        const BnGroup r = bn_group_finish(e.x, e.y, sums[2L * G * C + grp], eps, ab != nullptr, gamma, beta, c);
+        bn_group_store(r, grp * NG, NG, C, c, mr, ab);
+        if (rmean) bn_running_update(rm, rv, momentum, r, repeat);
+    }
+    if (rmean) { rmean[c] = rm; rvar[c] = rv; }
 }
 
 // backward means: red[n][c] = the group's {mean g, mean g * xhat} (zeros in eval mode, where the
@@ -364,18 +455,113 @@ extern "C" int irgan_bn_backward(const void* dy, int32_t dy_dtype, int32_t lddy,
     const dim3 g(nb, N);
     if (vec)
         bn_rows_kernel<1, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, nullptr, gamma, beta, nullptr, 0, 0, 0, HW, C,
-                                                rows, (float2*)work);
+                                                rows, (float2*)work, 0);
     else
         bn_rows_kernel<1, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, nullptr, gamma, beta, nullptr, 0, 0, 0, HW, C,
-                                                rows, (float2*)work);
+                                                rows, (float2*)work, 0);
     bn_bwd_finalize_kernel<<<irgan_cdiv(C, FC), FC * FS, 0, st>>>((const float2*)work, N, C, nb, HW, G, eval, red, dgamma,
                                                                   dbeta);
     if (vec)
         bn_rows_kernel<2, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, red, gamma, beta, dx, dx_dtype, lddx, dxoff, HW, C,
-                                                rows, nullptr);
+                                                rows, nullptr, 0);
     else
         bn_rows_kernel<2, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, red, gamma, beta, dx, dx_dtype, lddx, dxoff, HW, C,
-                                                rows, nullptr);
+                                                rows, nullptr, 0);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- SyncBN entry points ----
+
+extern "C" int irgan_bn_sync_sums(const void* x, int32_t dtype, int32_t N, int32_t HW, int32_t C, int32_t ld,
+                                  int32_t off, int32_t G, int32_t nb, double* work, double* sums, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!work || !sums || G < 1 || N % G || nb < 0 || nb > IRGAN_IN_PARTS) return IRGAN_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    if (nb > 0) {   // the conv epilogue's float2 partials
+        bn_sync_sums_kernel<float2><<<irgan_cdiv(C, FC), FC * FS, 0, st>>>((const float2*)work, N, C, nb, HW, G, sums,
+                                                                           nullptr, nullptr);
+        IRGAN_LAUNCH_CHECK();
+        return 0;
+    }
+    if (!x || !dt_ok(dtype) || !slice_ok(C, ld, off)) return IRGAN_EINVAL;
+    const bool vec = vec_ok(C, {ld, off});
+    const RowGrid rg = bn_grid(N, HW, C, vec);
+    const Slice X{x, dtype, ld, off};
+    const dim3 g(rg.nb, N);
+    if (vec)
+        bn_stats_kernel<V><<<g, TPB, 0, st>>>(X, HW, C, rg.rows, (double2*)work);
+    else
+        bn_stats_kernel<1><<<g, TPB, 0, st>>>(X, HW, C, rg.rows, (double2*)work);
+    bn_sync_sums_kernel<double2><<<irgan_cdiv(C, FC), FC * FS, 0, st>>>((const double2*)work, N, C, rg.nb, HW, G, sums,
+                                                                        nullptr, nullptr);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_sync_finalize(const double* sums, int32_t N, int32_t C, int32_t G, const float* gamma,
+                                      const float* beta, float* running_mean, float* running_var, float momentum,
+                                      float eps, int32_t repeat, float* mr, float* ab, irgan_stream_t s) {
+    if ((long)N * C <= 0) return 0;
+    if (!sums || !mr || G < 1 || N % G || repeat < 1 || (ab && (!gamma || !beta)) || (!running_mean != !running_var))
+        return IRGAN_EINVAL;
+    bn_sync_finalize_kernel<<<irgan_cdiv(C, 64), 64, 0, (hipStream_t)s>>>(sums, N, C, G, gamma, beta, running_mean,
+                                                                         running_var, momentum, eps, repeat, mr, ab);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_sync_backward_sums(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff,
+                                           const void* dy2, int32_t dy2_dtype, int32_t lddy2, int32_t dy2off,
+                                           const void* x, int32_t x_dtype, int32_t ldx, int32_t xoff, int32_t act,
+                                           int32_t N, int32_t HW, int32_t C, int32_t G, const float* mr,
+                                           const float* gamma, const float* beta, double* work, double* bsums,
+                                           float* dgamma, float* dbeta, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!dy || !x || !mr || !gamma || !beta || !work || !bsums || !dt_ok(dy_dtype) || !dt_ok(x_dtype) ||
+        (dy2 && !dt_ok(dy2_dtype)) || G < 1 || N % G || !act_ok(act) || !slice_ok(C, lddy, dyoff) ||
+        !slice_ok(C, ldx, xoff) || (dy2 && !slice_ok(C, lddy2, dy2off)))
+        return IRGAN_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
+    const RowGrid rg = bn_grid(N, HW, C, vec);
+    const Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
+    const dim3 g(rg.nb, N);
+    if (vec)
+        bn_rows_kernel<1, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, nullptr, gamma, beta, nullptr, 0, 0, 0, HW, C,
+                                                rg.rows, (float2*)work, 0);
+    else
+        bn_rows_kernel<1, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, nullptr, gamma, beta, nullptr, 0, 0, 0, HW, C,
+                                                rg.rows, (float2*)work, 0);
+    bn_sync_sums_kernel<float2><<<irgan_cdiv(C, FC), FC * FS, 0, st>>>((const float2*)work, N, C, rg.nb, HW, G, bsums,
+                                                                       dgamma, dbeta);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_bn_sync_backward_dx(const void* dy, int32_t dy_dtype, int32_t lddy, int32_t dyoff,
+                                         const void* dy2, int32_t dy2_dtype, int32_t lddy2, int32_t dy2off,
+                                         const void* x, int32_t x_dtype, int32_t ldx, int32_t xoff, int32_t act,
+                                         int32_t N, int32_t HW, int32_t C, int32_t G, const float* mr,
+                                         const float* gamma, const float* beta, const double* bsums, void* dx,
+                                         int32_t dx_dtype, int32_t lddx, int32_t dxoff, irgan_stream_t s) {
+    if ((long)N * HW * C <= 0) return 0;
+    if (!dy || !x || !mr || !gamma || !beta || !bsums || !dx || !dt_ok(dy_dtype) || !dt_ok(x_dtype) ||
+        !dt_ok(dx_dtype) || (dy2 && !dt_ok(dy2_dtype)) || G < 1 || N % G || !act_ok(act) ||
+        !slice_ok(C, lddy, dyoff) || !slice_ok(C, ldx, xoff) || !slice_ok(C, lddx, dxoff) ||
+        (dy2 && !slice_ok(C, lddy2, dy2off)))
+        return IRGAN_EINVAL;
+    hipStream_t st = (hipStream_t)s;
+    const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff, lddx, dxoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
+    const RowGrid rg = bn_grid(N, HW, C, vec);
+    const Slice X{x, x_dtype, ldx, xoff}, DY{dy, dy_dtype, lddy, dyoff}, DY2{dy2, dy2_dtype, lddy2, dy2off};
+    const dim3 g(rg.nb, N);
+    if (vec)
+        bn_rows_kernel<3, V><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, (const float*)bsums, gamma, beta, dx, dx_dtype,
+                                                lddx, dxoff, HW, C, rg.rows, nullptr, N / G);
+    else
+        bn_rows_kernel<3, 1><<<g, TPB, 0, st>>>(X, DY, DY2, act, mr, (const float*)bsums, gamma, beta, dx, dx_dtype,
+                                                lddx, dxoff, HW, C, rg.rows, nullptr, N / G);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -457,9 +457,35 @@ class NoNorm(INLayer):
         if db is not None:
             ops.channel_sum(dx, db)
 
+class BNSync:
+    """The SyncBN handle of BNLayer: the process group whose ranks share BatchNorm statistics
+    (``group`` None is the default group, so "no synchronisation" is a missing handle, not a
+    None group).  ``all_reduce`` sums an fp64 device buffer over the ranks in place, as a
+    synchronous-semantics collective on the CURRENT stream: the layer's next kernel on that
+    stream reads the reduced values.  Every rank issues these calls in program order -- the
+    same order on all of them -- so they pair up with each other across the main and the side
+    stream and with the asynchronous gradient buckets (BucketedAllreduce) on the same group.
+    RCCL ('nccl') reduces the device tensor; any other backend (gloo in the tests) is staged
+    through the host, as replicas_identical does."""
+
+    def __init__(self, group=None):
+        import torch.distributed as dist
+        self.group = group
+        self.on_device = dist.get_backend(group) == "nccl"
+
+    def all_reduce(self, t: torch.Tensor):
+        import torch.distributed as dist
+        if self.on_device:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            return
+        h = t.cpu()                # waits for the current stream's local sums
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+        t.copy_(h)                 # on the current stream, in front of the finishing half
+
+
 class BNLayer(INLayer):
     """norm='batch' (ir:158-159: nn.BatchNorm2d, eps 1e-5, momentum 0.1, affine, running
-    statistics) on one device; the conv in front has no bias (ir:450-455, 588-593).  Same
+    statistics); the conv in front has no bias (ir:450-455, 588-593).  Same
     interface as INLayer.  gamma / beta (and their gradients) are the layer's slices of the
     ParamStore flat buffers, so Adam, the optimizer state and the gradient reduce cover them
     like any conv weight; the running buffers are ``store.buffers`` tensors.
@@ -470,7 +496,17 @@ class BNLayer(INLayer):
     the groups in that order.  ``repeat``: the running update of one forward applied that many
     times, for a forward that stands for several identical ones of the reference (the fused step
     runs G once where ir:1638 and ir:1657 run it twice on the same weights and input).
-    ``training`` False: the running statistics normalise and nothing is updated (model.eval())."""
+    ``training`` False: the running statistics normalise and nothing is updated (model.eval()).
+
+    ``sync`` (a BNSync, or None: the local batch): in training mode the statistics of a group are
+    those of the group's samples on every rank of the handle's process group, nn.SyncBatchNorm's
+    semantics.  The forward runs local sums -> one all-reduce(SUM) of groups * (2C + 1) doubles ->
+    finish, the backward the same with {sum g, sum g * xhat}; the buffers are this layer's own
+    entries of ``bufs`` ("bnsync_" / "bnsyncb_" + name), never a shared scratch: BatchNorm layers
+    run on the main and on the side stream, and the collective is asynchronous to the host.
+    Every rank finishes from the same reduced bytes, so tables and running buffers stay
+    bit-identical over the replicas.  dgamma / dbeta take the LOCAL sums: they lie in the flat
+    gradient buffer, whose all-reduce averages them as DDP does around nn.SyncBatchNorm."""
 
     def __init__(self, store: "ParamStore", key: str):
         self.store, self.key = store, key
@@ -480,23 +516,31 @@ class BNLayer(INLayer):
         self.running_mean = store.buffers[key + ".running_mean"]
         self.running_var = store.buffers[key + ".running_var"]
         self.num_batches_tracked = store.buffers[key + ".num_batches_tracked"]
-        self.training, self.groups, self.repeat = True, 1, 1
+        self.training, self.groups, self.repeat, self.sync = True, 1, 1, None
 
-    def configure(self, training=True, groups=1, repeat=1):
-        self.training, self.groups, self.repeat = bool(training), int(groups), int(repeat)
+    def configure(self, training=True, groups=1, repeat=1, sync: BNSync = None):
+        self.training, self.groups, self.repeat, self.sync = bool(training), int(groups), int(repeat), sync
 
     def _tables(self, bufs: Buffers, name: str, x: Feat, nb=0, want_ab=False):
         """x's {mean, rstd} table (kept for bwd()) and, if asked, the {shift, scale} one."""
         N, C = x.N, x.C
         mr = bufs.get("mr_" + name, (N * C * ops.BN_TABLE,), torch.float32)
         ab = bufs.get("ab_" + name, (N * C * 2,), torch.float32) if want_ab else None
-        bufs.state["bn_" + name] = (self.training, self.groups)
+        sync = self.sync if self.training else None   # eval mode reads no batch statistics
+        bufs.state["bn_" + name] = (self.training, self.groups, sync)
         if not self.training:
             ops.bn_eval_table(self.running_mean, self.running_var, self.gamma, self.beta, N, mr, ab)
             return mr, ab
         work = self._work(bufs, N, C)
-        ops.bn_stats(x, work, mr, self.groups, self.gamma, self.beta, self.running_mean, self.running_var, self.repeat,
-                     ab=ab, nb=nb)
+        if sync is not None:
+            sums = bufs.get("bnsync_" + name, (ops.bn_sync_numel(self.groups, C),), torch.float64)
+            ops.bn_sync_sums(x, work, sums, self.groups, nb=nb)
+            sync.all_reduce(sums)
+            ops.bn_sync_finalize(sums, N, C, mr, self.groups, self.gamma, self.beta, self.running_mean,
+                                 self.running_var, self.repeat, ab=ab)
+        else:
+            ops.bn_stats(x, work, mr, self.groups, self.gamma, self.beta, self.running_mean, self.running_var,
+                         self.repeat, ab=ab, nb=nb)
         self.num_batches_tracked += self.repeat * self.groups
         return mr, ab
 
@@ -541,9 +585,18 @@ class BNLayer(INLayer):
     def bwd(self, bufs, name, dy, z, act, dx, db=None, dy2=None, q8=None, wgrad=True):
         if q8 is not None:
             self._no_fp8()
-        training, groups = bufs.state["bn_" + name]
+        training, groups, sync = bufs.state["bn_" + name]
         N, C = z.N, z.C
         work = self._work(bufs, N, C)
+        if sync is not None:   # the forward was synchronised: so are the dx means (wgrad or not)
+            mr = bufs.d["mr_" + name]
+            bsums = bufs.get("bnsyncb_" + name, (ops.bn_sync_numel(groups, C),), torch.float64)
+            ops.bn_sync_backward_sums(dy, z, act, mr, self.gamma, self.beta, work, bsums,
+                                      dgamma=self.dgamma if wgrad else None, dbeta=self.dbeta if wgrad else None,
+                                      groups=groups, dy2=dy2)
+            sync.all_reduce(bsums)
+            ops.bn_sync_backward_dx(dy, z, act, mr, self.gamma, self.beta, bsums, dx, groups=groups, dy2=dy2)
+            return
         red = self._red(bufs, N, C)
         ops.bn_backward(dy, z, act, bufs.d["mr_" + name], self.gamma, self.beta, work, red, dx,
                         dgamma=self.dgamma if wgrad else None, dbeta=self.dbeta if wgrad else None, groups=groups,
@@ -553,9 +606,10 @@ class BNLayer(INLayer):
 def make_norm(norm: str, store: "ParamStore" = None, key: str = None) -> INLayer:
     """The engine's per-layer norm for Config.norm (ir:154-165): 'instance', 'none' or 'batch'.
     'batch' (BNLayer) takes the layer's ParamStore and the state key of its nn.BatchNorm2d
-    module; it is single-device BatchNorm (statistics over the local batch) -- under a process
-    group of more than one rank the reference semantics would need SyncBN, the one remaining
-    gap (GANTrainer refuses that combination)."""
+    module.  Its statistics are the local batch's unless the layer is handed a BNSync handle
+    (BNLayer.sync): GANStep does that for the fused step under Config.sync_bn with more than one
+    data-parallel rank, where the reference semantics need the global batch (SyncBN); without
+    the option GANTrainer refuses that combination."""
     if norm == "instance":
         return INLayer()
     if norm in ("none", None):
@@ -602,6 +656,7 @@ class GeneratorEngine:
         self.norm_type, self.padding_type, self.use_dropout = norm, padding_type, bool(use_dropout)
         self.dropout_seed, self.dropout_calls = int(dropout_seed), 0
         self.training = True
+        self.bn_sync = None   # BNSync handle of the fused step's forwards (GANStep, Config.sync_bn)
         self.input_nc, self.output_nc, self.n_blocks = input_nc, output_nc, n_blocks
         self.no_aa, self.no_aa_up = no_antialias, no_antialias_up
         self.tdt = ops.TORCH_DT[dtype]
@@ -708,18 +763,21 @@ class GeneratorEngine:
         return res, res and self.fp8_ud and ok(H1, W1, c2 + c1)
 
     def forward(self, ir_nchw: torch.Tensor, bufs: Buffers = None, training: bool = None,
-                bn_repeat: int = 1) -> torch.Tensor:
+                bn_repeat: int = 1, bn_sync: bool = False) -> torch.Tensor:
         """ir (B, input_nc, H, W) fp32 in [-1,1] -> fake NHWC fp32 (B, H, W, 3).
         Activations land in ``bufs`` (default: the engine's own set).  ``training``
         (default: self.training) decides nn.Dropout's and nn.BatchNorm2d's mode (ir:394-395):
         callers outside the module forward / GANStep pass the module's train()/eval() state.
-        bn_repeat: BatchNorm's running update applied that many times (BNLayer.repeat)."""
+        bn_repeat: BatchNorm's running update applied that many times (BNLayer.repeat).
+        bn_sync: synchronise the BatchNorm statistics over the engine's ``bn_sync`` handle (if it
+        has one; GANStep's forwards) -- every other caller, the module API among them, normalises
+        with the local batch, as nn.BatchNorm2d does under DDP."""
         B, _, H, W = ir_nchw.shape
         g, T = bufs or self.bufs, self.tdt
         train = self.training if training is None else bool(training)
         if self.norm_type == "batch":
             for n in self.norms.values():
-                n.configure(training=train, groups=1, repeat=bn_repeat)
+                n.configure(training=train, groups=1, repeat=bn_repeat, sync=self.bn_sync if bn_sync else None)
         c0, c1, c2 = self.ngf, 2 * self.ngf, 4 * self.ngf
         H1, W1, H2, W2 = self._dims(H, W)
         g.state["shape"] = (B, H, W)
@@ -1037,6 +1095,7 @@ class DiscriminatorEngine:
         self.norms = [make_norm(norm, store, f"model.{int(k.split('.')[1]) + 1}") if n else None
                       for (k, _, n) in self.LAYERS]
         self.norm_type, self.training = norm, True
+        self.bn_sync = None   # BNSync handle of the fused step's forwards (GANStep, Config.sync_bn)
         self.bufs = Buffers(store.device)
 
     def pack(self):
@@ -1044,16 +1103,18 @@ class DiscriminatorEngine:
             self._pack_batch = ops.PackBatch(self.packs)
         self._pack_batch.run()
 
-    def forward(self, din: Feat, tag="", bufs: Buffers = None, groups: int = 1) -> torch.Tensor:
+    def forward(self, din: Feat, tag="", bufs: Buffers = None, groups: int = 1, bn_sync: bool = False) -> torch.Tensor:
         """din: NHWC (NB, H, W, 4) compute-dtype -> patch logits (NB, h, w, 1) fp32.
         The activations are kept in ``bufs`` (default: the engine's own) under ``tag``.
         groups: BatchNorm statistics per group of NB / groups samples (BNLayer.groups);
-        self.training: BatchNorm's train() / eval() mode."""
+        self.training: BatchNorm's train() / eval() mode; bn_sync: as GeneratorEngine.forward
+        (each group is synchronised separately)."""
         g, T = bufs or self.bufs, self.tdt
         if self.norm_type == "batch":
             for nrm in self.norms:
                 if nrm is not None:
-                    nrm.configure(training=self.training, groups=groups, repeat=1)
+                    nrm.configure(training=self.training, groups=groups, repeat=1,
+                                  sync=self.bn_sync if bn_sync else None)
         x = din
         acts, pre = [din], {}
         g.state[tag] = (acts, pre)
@@ -1382,6 +1443,12 @@ class GANStep:
         self.pg = process_group
         self.g_reduce = BucketedAllreduce(G, process_group, force=force_reduce)
         self.d_reduce = BucketedAllreduce(D, process_group, force=force_reduce)
+        # SyncBN (Config.sync_bn): wherever the gradient collectives run, the BatchNorm layers of
+        # both networks take their training statistics over the same ranks -- all four forwards
+        # of step() and their backwards; groups / repeat rules unchanged.  Without a process group,
+        # or at world size 1 without force_reduce, the plain local path runs.
+        if cfg.norm == "batch" and getattr(cfg, "sync_bn", False) and self.g_reduce.active:
+            self.gen.bn_sync = self.dis.bn_sync = BNSync(process_group)
         self.lr_scale = 1.0
         # the D step (D forward/backward on [real; fake] and its all-reduce) runs on a
         # side stream, concurrently with the G-step terms that do not read D (L1,
@@ -1446,8 +1513,8 @@ class GANStep:
         # BatchNorm: the one forward stands for the reference's two training-mode forwards, so its
         # running update is applied twice (with dropout the two forwards update once each)
         self.gen.training = self.dis.training = True
-        fake_d = self.gen.forward(ir, bufs=self.dbufs) if self.gen.use_dropout else None
-        fake = self.gen.forward(ir, bn_repeat=1 if self.gen.use_dropout else 2)
+        fake_d = self.gen.forward(ir, bufs=self.dbufs, bn_sync=True) if self.gen.use_dropout else None
+        fake = self.gen.forward(ir, bn_repeat=1 if self.gen.use_dropout else 2, bn_sync=True)
         # ---- D step on [real; fake] as one 2B batch (ir:1636-1651), on the side stream
         dfake = b.get("dfake", (B, H, W, cout), torch.float32)
 
@@ -1489,7 +1556,8 @@ class GANStep:
             # -0.8 %: the G forward slowed by what it took off the join, profiles/r05_ab1_dsplit.txt)
             self.D.zero_grad()
             ops.axpby(Feat(fake if fake_d is None else fake_d), 1.0, Feat(din.t[B:], cin, cout))
-            pred = self.dis.forward(din, tag="d", groups=2)   # BatchNorm: netD(real), netD(fake) statistics
+            # BatchNorm: netD(real), netD(fake) statistics (under SyncBN each group over all ranks)
+            pred = self.dis.forward(din, tag="d", groups=2, bn_sync=True)
             dpred = b.get("dpred", tuple(pred.shape), torch.float32)
             ops.hinge(pred, pred[:B].numel(), 0, 1.0, dpred, L[0:1])
             # D grads reduced tail-first under the D backward (8 MB buckets: model.8 + the head
@@ -1506,7 +1574,7 @@ class GANStep:
             # when the D step saw the other dropout draw)
             if fake_d is not None:
                 ops.axpby(Feat(fake), 1.0, Feat(din.t[B:], cin, cout))
-            predg = self.dis.forward(din.batch(B, B), tag="g")
+            predg = self.dis.forward(din.batch(B, B), tag="g", bn_sync=True)
             dpg = b.get("dpredg", tuple(predg.shape), torch.float32)
             ops.hinge(predg, predg.numel(), 1, cfg.lambda_gan, dpg, L[1:2])
             dd = self.dis.backward(dpg, want_wgrad=False, want_dinput=True, tag="g")

@@ -101,6 +101,8 @@ class Config:
         self.log_every = 50
         self.test_batch = 16             # run_test: frames per generator call (the reference runs one)
         self.deterministic = False       # ops.set_deterministic: bitwise-reproducible weight gradients
+        self.sync_bn = False             # norm='batch' under data parallelism: BatchNorm statistics over all
+                                         # ranks (nn.SyncBatchNorm semantics) in the fused step; off -> refused
 
 
 # =============================================================================
@@ -114,8 +116,9 @@ class Identity(nn.Module):
 
 def get_norm_layer(norm_type="instance"):
     """ir:154-165.  The HIP engines implement all three: 'instance' (the reference default),
-    'none' and 'batch' (nn.BatchNorm2d on one device: engine.BNLayer; with more than one
-    data-parallel rank it would have to be SyncBN, which GANTrainer refuses)."""
+    'none' and 'batch' (nn.BatchNorm2d: engine.BNLayer; with more than one data-parallel rank
+    the fused step synchronises its statistics under Config.sync_bn, and GANTrainer refuses
+    the combination without it)."""
     if norm_type == "batch":
         return nn.BatchNorm2d
     if norm_type == "instance":
@@ -333,7 +336,9 @@ class ResnetUNetGenerator(_StoreModule):
     """ir:425-569.  forward(x) -> (out, None).  Input (B, input_nc, H, W) in
     [-1,1] on the HIP device, any H, W >= 2: when H or W is not divisible by 4 the
     decoder resizes the up-sampled map to the skip's size as the reference does
-    (ir:555-556, 562-563)."""
+    (ir:555-556, 562-563).  Under norm='batch' a call normalises with the LOCAL batch, also
+    inside a process group and whatever Config.sync_bn says (as nn.BatchNorm2d under DDP): only
+    GANTrainer's fused step synchronises the statistics."""
 
     def __init__(self, input_nc, output_nc, ngf=64, norm_layer=nn.InstanceNorm2d, use_dropout=False, n_blocks=9,
                  padding_type="reflect", no_antialias=False, no_antialias_up=False, device=None,
@@ -422,7 +427,9 @@ class _DFn(torch.autograd.Function):
 class NLayerDiscriminator(_StoreModule):
     """ir:576-635: any n_layers >= 1 (train_kaist builds 3), norm 'instance', 'none' or 'batch'.
     Under norm='batch' every call normalises with its own batch's statistics and updates the
-    running buffers once (netD(real), netD(fake): two updates, ir:1642-1643)."""
+    running buffers once (netD(real), netD(fake): two updates, ir:1642-1643) -- the LOCAL batch,
+    also inside a process group (as nn.BatchNorm2d under DDP): only GANTrainer's fused step
+    synchronises the statistics (Config.sync_bn)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.InstanceNorm2d, device=None,
                  compute_dtype="bf16"):
@@ -626,16 +633,21 @@ class IRColorizationModel(nn.Module):
 # =============================================================================
 
 def _refuse_multi_rank_batch_norm(cfg, process_group=None):
-    """norm='batch' normalises with the LOCAL batch's statistics: with more than one
-    data-parallel rank the reference semantics need SyncBN, which is not implemented."""
+    """norm='batch' without Config.sync_bn normalises with the LOCAL batch's statistics: with more
+    than one data-parallel rank the reference semantics need SyncBN (statistics over the global
+    batch), which is opt-in -- cfg.sync_bn = True makes the fused step synchronise them
+    (engine.BNSync) and this check return; left off, the combination is refused rather than
+    trained with per-rank statistics."""
     import torch.distributed as dist
     if getattr(cfg, "norm", "instance") != "batch" or not (dist.is_available() and dist.is_initialized()):
+        return
+    if getattr(cfg, "sync_bn", False):
         return
     world = dist.get_world_size(process_group)
     if world > 1:
         raise NotImplementedError(f"norm='batch' with {world} data-parallel ranks needs SyncBN (statistics over the "
-                                  "global batch), which the HIP engines do not implement: train on one device, or "
-                                  "use norm='instance' / 'none'")
+                                  "global batch): set cfg.sync_bn = True, train on one device, or use "
+                                  "norm='instance' / 'none'")
 
 
 class GANTrainer:

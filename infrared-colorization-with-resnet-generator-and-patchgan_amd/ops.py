@@ -753,6 +753,50 @@ def bn_backward(dy: Feat, x: Feat, act: int, mr, gamma, beta, work, red, dx: Fea
               P(dgamma), P(dbeta), stream())
 
 
+# SyncBN: the passes above cut into a local half (fp64 sums) and a finishing half (from the sums
+# the caller has all-reduced).  One buffer per pass: sums[G][C][2] then cnt[G] doubles.
+
+def bn_sync_numel(groups: int, C: int) -> int:
+    """Doubles of a SyncBN sums buffer: {sum, sum} per (group, channel) + the count per group."""
+    return groups * (2 * C + 1)
+
+
+def bn_sync_sums(x: Feat, work: torch.Tensor, sums: torch.Tensor, groups=1, nb=0):
+    """Forward, local half: sums[g][c] = {sum x, sum x^2} over the local samples of group g and
+    cnt[g] = their element count.  nb > 0: ``work`` holds nb conv-epilogue partials per image."""
+    assert x.N % groups == 0 and sums.dtype == torch.float64 and sums.numel() >= bn_sync_numel(groups, x.C)
+    _lib.call("irgan_bn_sync_sums", x.ptr, x.dt, x.N, x.H * x.W, x.C, x.ld, x.off, groups, nb, P(work), P(sums),
+              stream())
+
+
+def bn_sync_finalize(sums: torch.Tensor, N: int, C: int, mr: torch.Tensor, groups=1, gamma=None, beta=None,
+                     running_mean=None, running_var=None, repeat=1, ab=None):
+    """Forward, finishing half, from the REDUCED sums: the tables of the N local samples and the
+    running update with the global mean / unbiased variance (bn_stats' arguments)."""
+    assert N % groups == 0 and repeat >= 1 and sums.dtype == torch.float64 and sums.numel() >= bn_sync_numel(groups, C)
+    _lib.call("irgan_bn_sync_finalize", P(sums), N, C, groups, P(gamma), P(beta), P(running_mean), P(running_var),
+              BN_MOMENTUM, BN_EPS, repeat, P(mr), P(ab), stream())
+
+
+def bn_sync_backward_sums(dy: Feat, x: Feat, act: int, mr, gamma, beta, work, bsums: torch.Tensor, dgamma=None,
+                          dbeta=None, groups=1, dy2: Feat = None):
+    """Backward, local half: bsums[g][c] = {sum g, sum g * xhat} and the counts; dgamma / dbeta
+    (optional) take the LOCAL sums -- the gradient all-reduce averages them like any weight's."""
+    assert x.N % groups == 0 and bsums.dtype == torch.float64 and bsums.numel() >= bn_sync_numel(groups, x.C)
+    d2 = (dy2.ptr, dy2.dt, dy2.ld, dy2.off) if dy2 is not None else (None, 0, 0, 0)
+    _lib.call("irgan_bn_sync_backward_sums", dy.ptr, dy.dt, dy.ld, dy.off, *d2, x.ptr, x.dt, x.ld, x.off, act, x.N,
+              x.H * x.W, x.C, groups, P(mr), P(gamma), P(beta), P(work), P(bsums), P(dgamma), P(dbeta), stream())
+
+
+def bn_sync_backward_dx(dy: Feat, x: Feat, act: int, mr, gamma, beta, bsums: torch.Tensor, dx: Feat, groups=1,
+                        dy2: Feat = None):
+    """Backward, finishing half: dx from the REDUCED bsums (the means over the reduced count)."""
+    assert x.N % groups == 0 and bsums.dtype == torch.float64 and bsums.numel() >= bn_sync_numel(groups, x.C)
+    d2 = (dy2.ptr, dy2.dt, dy2.ld, dy2.off) if dy2 is not None else (None, 0, 0, 0)
+    _lib.call("irgan_bn_sync_backward_dx", dy.ptr, dy.dt, dy.ld, dy.off, *d2, x.ptr, x.dt, x.ld, x.off, act, x.N,
+              x.H * x.W, x.C, groups, P(mr), P(gamma), P(beta), P(bsums), dx.ptr, dx.dt, dx.ld, dx.off, stream())
+
+
 # ----------------------------------------------------------------------------
 # resampling / elementwise
 # ----------------------------------------------------------------------------
