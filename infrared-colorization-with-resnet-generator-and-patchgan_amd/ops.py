@@ -1094,11 +1094,22 @@ def l1(a: torch.Tensor, b: torch.Tensor, w: float, ga: torch.Tensor, loss: torch
               dt_code(ga) if ga is not None else 0, int(accumulate), P(loss), stream())
 
 
+def _whole(x: Feat, what: str):
+    """irgan_tv / irgan_ssim_ws take (ptr, N, H, W, C) and read the image as contiguous: a
+    channel slice (ld != C or off != 0) would be read as if it were whole, so refuse it."""
+    if x.off != 0 or x.ld != x.C:
+        raise ValueError(f"{what} reads a contiguous NHWC image, not a channel slice "
+                         f"(off {x.off}, C {x.C}, ld {x.ld})")
+
+
 def tv(x: Feat, w: float, g: torch.Tensor, loss: torch.Tensor):
+    _whole(x, "ops.tv: x")
     _lib.call("irgan_tv", x.ptr, x.N, x.H, x.W, x.C, ctypes.c_float(w), P(g), P(loss), stream())
 
 
 def ssim(a: Feat, b: Feat, w: float, g: torch.Tensor, loss: torch.Tensor, work: torch.Tensor, window: int = 11):
+    _whole(a, "ops.ssim: a")
+    _whole(b, "ops.ssim: b")
     _lib.call("irgan_ssim_ws", a.ptr, b.ptr, a.N, a.H, a.W, a.C, ctypes.c_float(w), P(g), P(loss), P(work), window,
               stream())
 
