@@ -21,6 +21,7 @@ import math
 import os
 from collections import OrderedDict
 from contextlib import nullcontext as _nullcontext
+from typing import NamedTuple
 
 import torch
 
@@ -344,75 +345,76 @@ class INLayer:
         """nb > 0: x's statistics partials are already in the shared work buffer
         (written by the producing conv, conv_fwd); only the reduction runs.
         The {mean, rstd} table stays in ``bufs`` under ``name`` for bwd().
-        q8: also write y's fp8 copy (ops.in_apply)."""
-        N, C = x.N, x.C
-        work = self._work(bufs, N, C)
-        mr = bufs.get("mr_" + name, (N * C * 2,), torch.float32)
+        q8 (an ops.Fp8Out): also write y's fp8 copy (ops.in_apply)."""
+        mr = self._stats(bufs, name, x, nb)
+        ops.in_apply(x, mr, y, act=act, res=res, xhat=xhat, q8=q8 and q8.side)
+        if q8 is not None:
+            q8.finish(y)
+
+    def _stats(self, bufs: Buffers, name: str, x: Feat, nb):
+        """x's {mean, rstd} table (kept for bwd()), from the nb partials per image a conv left
+        in the work buffer or, with none, from a statistics pass over x."""
+        work = self._work(bufs, x.N, x.C)
+        mr = bufs.get("mr_" + name, (x.N * x.C * 2,), torch.float32)
         if nb:
             ops.in_finalize(x, work, nb, mr)
         else:
             ops.in_stats(x, work, mr)
-        ops.in_apply(x, mr, y, act=act, res=res, xhat=xhat, q8=q8)
+        return mr
 
-    def conv_fwd8(self, bufs: Buffers, name: str, pc, w8, dqw, x8: Feat, dqx, z: Feat, y: Feat, act,
-                  res: Feat = None, q8=None):
-        """conv_fwd on fp8 operands (ops.conv_fwd_fp8) with the fused statistics."""
+    def _conv(self, bufs: Buffers, pc, x: Feat, z: Feat, conv8=None):
+        """z = conv(x); returns the statistics partials per image the conv's epilogue left in the
+        work buffer (0: none).  conv8 = (w8, dqw, x8, dqx): the conv on fp8 operands
+        (ops.conv_fwd_fp8; x unused) -- the one way a norm layer is handed an fp8 conv."""
         work = self._work(bufs, z.N, z.C)
-        nb = ops.conv_fwd_fp8(pc, w8, dqw, x8, dqx, z, part=work)
-        self.fwd(bufs, name, z, y, act, res=res, nb=nb, q8=q8)
-
-    def conv_fwd(self, bufs: Buffers, name: str, pc, x: Feat, z: Feat, y: Feat, act, res: Feat = None):
-        """z = conv(x) (kept for the backward), y = act(IN(z) [+ res]): the IN statistics
-        come from the conv's epilogue when it has a fused kernel (ops.conv_fwd_stats)."""
-        work = self._work(bufs, z.N, z.C)
+        if conv8 is not None:
+            w8, dqw, x8, dqx = conv8
+            return ops.conv_fwd_fp8(pc, w8, dqw, x8, dqx, z, part=work)
         nb = ops.conv_fwd_stats(pc, x, z, work) if INLayer.fused_stats else 0
         if not nb:
             ops.conv_fwd(pc, x, z)
-        self.fwd(bufs, name, z, y, act, res=res, nb=nb)
+        return nb
+
+    def conv_fwd(self, bufs: Buffers, name: str, pc, x: Feat, z: Feat, y: Feat, act, res: Feat = None, conv8=None,
+                 q8=None):
+        """z = conv(x) (kept for the backward), y = act(norm(z) [+ res]): the statistics come
+        from the conv's epilogue when it has a fused kernel (_conv)."""
+        self.fwd(bufs, name, z, y, act, res=res, nb=self._conv(bufs, pc, x, z, conv8), q8=q8)
 
     def conv_stats(self, bufs: Buffers, name: str, pc, x: Feat, z: Feat, conv8=None):
         """z = conv(x) and z's {mean, rstd} table (returned, kept for bwd()) -- no apply:
-        the consumer normalises on load (ops.blur_down_in / ops.upsample_in).
-        conv8 = (w8, dqw, x8, dqx): the conv on fp8 operands (ops.conv_fwd_fp8)."""
-        work = self._work(bufs, z.N, z.C)
-        mr = bufs.get("mr_" + name, (z.N * z.C * 2,), torch.float32)
-        if conv8 is not None:
-            w8, dqw, x8, dqx = conv8
-            ops.in_finalize(z, work, ops.conv_fwd_fp8(pc, w8, dqw, x8, dqx, z, part=work), mr)
-            return mr
-        nb = ops.conv_fwd_stats(pc, x, z, work) if INLayer.fused_stats else 0
-        if nb:
-            ops.in_finalize(z, work, nb, mr)
-        else:
-            ops.conv_fwd(pc, x, z)
-            ops.in_stats(z, work, mr)
-        return mr
+        the consumer normalises on load (ops.blur_down_in / ops.upsample_in)."""
+        return self._stats(bufs, name, z, self._conv(bufs, pc, x, z, conv8))
 
     def resample_fwd(self, bufs: Buffers, name: str, pc, x: Feat, z: Feat, a_name: str, act, y: Feat, fused, plain,
                      conv8=None, q8=None):
         """y = resample(act(IN(conv(x)))): the IN apply fused into the resample when
         ``fused(z, mr, act, y)`` takes the shapes, else apply into bufs[a_name] + ``plain``.
-        conv8: the conv on fp8 operands (conv_stats); q8: also y's e4m3 copy (Fp8Acts.spec)."""
+        conv8: the conv on fp8 operands (_conv); q8 (an ops.Fp8Out): also y's e4m3 copy."""
         mr = self.conv_stats(bufs, name, pc, x, z, conv8=conv8)
-        if INLayer.fused_resample and (fused(z, mr, act, y, q8=q8) if q8 is not None else fused(z, mr, act, y)):
-            return
-        a = Feat(bufs.get(a_name, (z.N, z.H, z.W, z.C), z.t.dtype))
-        ops.in_apply(z, mr, a, act=act)
-        plain(a, y)
+        side = q8.side if q8 is not None else None
+        taken = INLayer.fused_resample and (fused(z, mr, act, y, q8=side) if side is not None else
+                                            fused(z, mr, act, y))
+        if not taken:
+            a = Feat(bufs.get(a_name, (z.N, z.H, z.W, z.C), z.t.dtype))
+            ops.in_apply(z, mr, a, act=act)
+            plain(a, y)
         if q8 is not None:
-            ops.fp8_quant(y, *q8)
+            q8.finish(y, taken)
 
     def bwd(self, bufs: Buffers, name: str, dy: Feat, z: Feat, act, dx: Feat, db=None, dy2: Feat = None, q8=None,
             wgrad=True):
         """z: the PRE-norm input kept from forward; act: the activation after IN.
-        q8: also write dx's fp8 copy (ops.in_backward).  wgrad: accumulate the norm's own
-        parameter gradients (BNLayer; InstanceNorm has none)."""
+        q8 (an ops.Fp8Out): also write dx's fp8 copy (ops.in_backward).  wgrad: accumulate the
+        norm's own parameter gradients (BNLayer; InstanceNorm has none)."""
         N, C = z.N, z.C
         work = self._work(bufs, N, C)
         red = self._red(bufs, N, C)
         mr = bufs.d["mr_" + name]
         ops.in_backward(dy, z, act, mr, work, red, dx, db=db if INLayer.sum_bias_grad else None, dy2=dy2,
-                        q8=q8 if not INLayer.sum_bias_grad else None)
+                        q8=q8.side if q8 is not None and not INLayer.sum_bias_grad else None)
+        if q8 is not None:
+            q8.finish(dx)
 
 class NoNorm(INLayer):
     """norm='none' (ir:162-163: ``lambda num_features: Identity()``): the layer is just its
@@ -434,17 +436,14 @@ class NoNorm(INLayer):
             self._no_fp8()
         ops.in_apply(x, self._ident(bufs, name, x.N, x.C), y, act=act, res=res)
 
-    def conv_fwd8(self, *a, **kw):
-        self._no_fp8()
-
-    def conv_fwd(self, bufs, name, pc, x, z, y, act, res=None):
-        ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
-        self.fwd(bufs, name, z, y, act, res=res)
-
-    def conv_stats(self, bufs, name, pc, x, z, conv8=None):
+    def _conv(self, bufs, pc, x, z, conv8=None):
         if conv8 is not None:
             self._no_fp8()
         ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
+        return 0
+
+    def conv_stats(self, bufs, name, pc, x, z, conv8=None):
+        self._conv(bufs, pc, x, z, conv8)
         return self._ident(bufs, name, z.N, z.C)
 
     def bwd(self, bufs, name, dy, z, act, dx, db=None, dy2=None, q8=None, wgrad=True):
@@ -550,11 +549,10 @@ class BNLayer(INLayer):
         mr, _ = self._tables(bufs, name, x, nb)
         ops.bn_apply(x, mr, self.gamma, self.beta, y, act=act, res=res)
 
-    def conv_fwd8(self, *a, **kw):
-        self._no_fp8()
-
-    def _conv(self, bufs, pc, x, z):
+    def _conv(self, bufs, pc, x, z, conv8=None):
         """z = conv(x); the partials per image in the work buffer (0: none were written)."""
+        if conv8 is not None:
+            self._no_fp8()
         nb = 0
         if self.training and INLayer.fused_stats:
             nb = ops.conv_fwd_stats(pc, x, z, self._work(bufs, z.N, z.C))
@@ -562,15 +560,10 @@ class BNLayer(INLayer):
             ops.conv_fwd(pc, x, z, bias=pc.bias is not None)
         return nb
 
-    def conv_fwd(self, bufs, name, pc, x, z, y, act, res=None):
-        self.fwd(bufs, name, z, y, act, res=res, nb=self._conv(bufs, pc, x, z))
-
     def conv_stats(self, bufs, name, pc, x, z, conv8=None):
         """z = conv(x); returns the {shift, scale} table the fused resample consumers read with
         ops.NORM_AFFINE (the {mean, rstd} table stays in ``bufs`` for bwd())."""
-        if conv8 is not None:
-            self._no_fp8()
-        return self._tables(bufs, name, z, self._conv(bufs, pc, x, z), want_ab=True)[1]
+        return self._tables(bufs, name, z, self._conv(bufs, pc, x, z, conv8), want_ab=True)[1]
 
     def resample_fwd(self, bufs, name, pc, x, z, a_name, act, y, fused, plain, conv8=None, q8=None):
         if q8 is not None:
@@ -629,6 +622,151 @@ def res_conv_keys(padding_type="reflect", use_dropout=False):
     return first, second
 
 
+class Fp8Conv(NamedTuple):
+    """One conv of the fp8 path (fp8_plan): its parameter key, the indices of the e4m3 copies of
+    its forward and flipped weight images (Fp8Weights) and the scale slots (Fp8Acts) of its
+    operand and of its dY."""
+    key: str
+    w_fwd: int
+    w_flip: int
+    s_x: int
+    s_dy: int
+
+
+def fp8_plan(n_blocks: int, fp8_ud: bool):
+    """The fp8 layout of a generator, the one place that numbers it (table: DESIGN.md s.2): a
+    record per e4m3 conv -- the two convs of every ResnetBlock, then down2 and up1_conv when
+    ``fp8_ud`` -- and the named (start, count) slot ranges Fp8Acts.snapshot() / update() run
+    over.  down2 and up1_conv share the operand slot: down2 reads the x1 slice of up1_conv's
+    concat.  Pure host arithmetic, no device."""
+    n = n_blocks
+    k1, k2 = res_conv_keys()   # the fp8 path runs the default ResnetBlock
+    convs = []
+    for b in range(n):
+        convs.append(Fp8Conv(f"resblocks.{b}.conv_block.{k1}", 4 * b, 4 * b + 1, 2 * b, 2 * n + 2 * b + 1))
+        convs.append(Fp8Conv(f"resblocks.{b}.conv_block.{k2}", 4 * b + 2, 4 * b + 3, 2 * b + 1, 2 * n + 2 * b))
+    if fp8_ud:
+        convs.append(Fp8Conv("down2.0", 4 * n, 4 * n + 1, 4 * n, 4 * n + 2))
+        convs.append(Fp8Conv("up1_conv.0", 4 * n + 2, 4 * n + 3, 4 * n, 4 * n + 1))
+    slots = {"fwd": (0, 2 * n),         # the ResnetBlock convs' operands
+             "dy": (2 * n, 2 * n),      # their dY
+             "cat": (4 * n, 1),         # the [up(h) | x1] concat
+             "ud_dy": (4 * n + 1, 2),   # up1_conv's, down2's dY
+             "x1": (4 * n + 3, 1)}      # down2's own x1 copy on the calibration step
+    return convs, slots
+
+
+class Fp8Call:
+    """The fp8 side of one forward call, kept in ``bufs.state["fp8"]`` -- all its backward reads:
+    ``on``: which groups run on e4m3 for the call's shape ('res': the ResnetBlock convs, 'ud':
+    down2 / up1_conv; GeneratorEngine.fp8_layers); ``calib``: the first 'ud' step (current
+    scaling): down2 reads its own copy of x1 (``x1_8c``), scaled from x1 alone, for its forward
+    AND its weight gradient, and up1_conv's concat is then scaled as a whole; ``x8``: the e4m3
+    operand buffer by layer name, which the weight gradients re-read."""
+
+    def __init__(self, on_res, on_ud, calib):
+        self.on, self.calib, self.x1_8c, self.x8 = {"res": on_res, "ud": on_ud}, calib, None, {}
+
+
+class GenConv:
+    """A generator conv in front of its norm layer, as the step names it: the PackedConv, its
+    parameter key, the norm and, for the layers of fp8_plan, the record ``rec``.  Whether a call
+    runs the layer on e4m3 or on the engine's dtype is the Fp8Call's decision for the layer's
+    ``group``, taken once when the forward starts; the methods here are the same call either way.
+    ``xp``: buffer name of the ReplicationPad2d(1) copy of the input (padding 'replicate': the
+    conv reads it, it is kept for the weight gradient, and the input gradient is folded back);
+    ``dy8``: buffer name of dY's e4m3 copy; ``s_calib``: down2's slot of its own x1 copy."""
+
+    def __init__(self, eng, pc, key, name, group, rec=None, xp=None, dy8="dy8", s_calib=None):
+        self.eng, self.pc, self.key, self.name, self.group, self.rec = eng, pc, key, name, group, rec
+        self.norm, self.xp, self.dy8, self.s_calib = eng.norms[name], xp, dy8, s_calib
+
+    def _w8(self, k):
+        return self.eng.f8w.dst[k], ops.Pi(self.eng.f8w.dq, k)
+
+    def _x8(self, st, used=False):
+        """The e4m3 operand and the pointer to its dequantisation factor; ``used``: the one it
+        was made with, after the forward moved the slot on (Fp8Acts.snapshot)."""
+        A = self.eng.f8a
+        if st.calib and self.s_calib is not None:
+            return st.x1_8c, A.dqp(self.s_calib)
+        return st.x8[self.name], (A.dqp_used if used else A.dqp)(self.rec.s_x)
+
+    def _conv8(self, st):
+        return (*self._w8(self.rec.w_fwd), *self._x8(st)) if st.on[self.group] else None
+
+    def feed(self, st, x: Feat):
+        """The operand x from a producer without an e4m3 output: a quantise launch."""
+        if st.on[self.group]:
+            self.eng.f8a.quant(self.rec.s_x, x, st.x8[self.name])
+
+    def side(self, st, sl=None):
+        """The ``q8`` of the launch that produces this layer's operand (``sl`` = (off, C): the
+        channel slice of it that the launch writes); None on a bf16 call and on the calibration
+        step, where calibrate() quantises instead."""
+        if not st.on[self.group] or (st.calib and self.group == "ud"):
+            return None
+        x8 = st.x8[self.name]
+        return ops.Fp8Out(self.eng.f8a, self.rec.s_x, x8.sl(*sl) if sl else x8)
+
+    def calibrate(self, st, x: Feat):
+        """Calibration step: the operand's scale from x alone, then its quantisation."""
+        if st.calib and self.group == "ud":
+            slot, x8 = (self.s_calib, st.x1_8c) if self.s_calib is not None else (self.rec.s_x, st.x8[self.name])
+            self.eng.f8a.calibrate(slot, x, x8)
+
+    def fwd(self, g: Buffers, st, x: Feat, z: Feat, y: Feat, act, res: Feat = None, nxt: "GenConv" = None):
+        """z = conv(x) (kept for the backward), y = act(norm(z)) [+ res].  ``nxt``: the layer that
+        reads y; the norm's apply writes its e4m3 operand along."""
+        if self.xp:
+            xp = Feat(g.get(self.xp, (x.N, x.H + 2, x.W + 2, x.C), self.eng.tdt))
+            ops.pad(x, xp, 1, "replicate")
+            x = xp
+        self.norm.conv_fwd(g, self.name, self.pc, x, z, y, act, res=res, conv8=self._conv8(st),
+                           q8=nxt.side(st) if nxt else None)
+
+    def resample_fwd(self, g: Buffers, st, x: Feat, z: Feat, a_name, act, y: Feat, fused, plain):
+        """z = conv(x), y = resample(act(norm(z))) (INLayer.resample_fwd)."""
+        self.norm.resample_fwd(g, self.name, self.pc, x, z, a_name, act, y, fused, plain, conv8=self._conv8(st))
+
+    def bwd(self, g: Buffers, st, dy: Feat, z: Feat, act, dz: Feat, x: Feat, dx: Feat, accumulate=False, padbuf=None):
+        """Backward of fwd(): dz = the norm's backward of dy (in place when dz is dy), the weight
+        gradient from x and dz, dx (+)= backward-data of dz.  The bf16 ResnetBlock convs launch
+        the backward-data first, every other case the weight gradient."""
+        e, on = self.eng, st.on[self.group]
+        dz8 = Feat(g.get(self.dy8, (*dz.t.shape[:3], dz.C), torch.float8_e4m3fn)) if on else None
+        self.norm.bwd(g, self.name, dy, z, act, dz, db=e._bgrad(self.key + ".bias"),
+                      q8=ops.Fp8Out(e.f8a, self.rec.s_dy, dz8) if on else None)
+        if on:
+            self._wgrad(st, x, dz, dz8)
+            if self.s_calib is not None:
+                st.x1_8c = None   # the calibration step's x1 copy is released here
+            ops.conv_dgrad_fp8(self.pc, *self._w8(self.rec.w_flip), dz8, e.f8a.dqp(self.rec.s_dy), dz, dx,
+                               accumulate=accumulate)
+            return
+        if self.group != "res":
+            self._wgrad(st, x, dz)
+        if self.xp:
+            dxp = Feat(g.get("res_dxp", (dx.N, dx.H + 2, dx.W + 2, dx.C), e.tdt))
+            ops.conv_dgrad(self.pc, dz, dxp)
+            ops.pad_fold(dxp, dx, 1, "replicate", accumulate=accumulate)
+        else:
+            ops.conv_dgrad(self.pc, dz, dx, accumulate=accumulate, pad_buf=padbuf)
+        if self.group == "res":
+            self._wgrad(st, Feat(g.d[self.xp]) if self.xp else x, dz)
+
+    def _wgrad(self, st, x: Feat, dz: Feat, dz8: Feat = None):
+        """The weight gradient: on the e4m3 copies (the operand with the scale it was made
+        with), on x and dz where that kernel does not take the layer or the call is bf16."""
+        e = self.eng
+        dw = e.store.krsc(self.key + ".weight", e.store.grad)
+        if dz8 is not None:
+            x8, dqx = self._x8(st, used=True)
+            if ops.conv_wgrad_fp8(self.pc.spec, x8, dz8, dqx, e.f8a.dqp(self.rec.s_dy), dw):
+                return
+        ops.conv_wgrad(self.pc.spec, x, dz, dw, e.dtype)
+
+
 # ----------------------------------------------------------------------------
 # generator  (ir:425-569)
 # ----------------------------------------------------------------------------
@@ -666,12 +804,10 @@ class GeneratorEngine:
         self.inc = _pc(S, "inc.1", ConvSpec(input_nc, c0, 7, 1, 3, PAD_REFLECT), dtype, need_dgrad=False)
         self.down1 = _pc(S, "down1.0", ConvSpec(c0, c1, 3, sd, 1, PAD_ZERO), dtype)
         self.down2 = _pc(S, "down2.0", ConvSpec(c1, c2, 3, sd, 1, PAD_ZERO), dtype)
-        k1, k2 = res_conv_keys(padding_type, use_dropout)
-        self.res_keys = (k1, k2)
+        k1, k2 = self.res_keys = res_conv_keys(padding_type, use_dropout)
         rspec = {"reflect": ConvSpec(c2, c2, 3, 1, 1, PAD_REFLECT), "zero": ConvSpec(c2, c2, 3, 1, 1, PAD_ZERO),
                  "replicate": ConvSpec(c2, c2, 3, 1, 0, PAD_ZERO)}[padding_type]   # replicate: on the padded copy
-        self.res = [(_pc(S, f"resblocks.{b}.conv_block.{k1}", rspec, dtype),
-                     _pc(S, f"resblocks.{b}.conv_block.{k2}", rspec, dtype)) for b in range(n_blocks)]
+        res = [_pc(S, f"resblocks.{b}.conv_block.{k}", rspec, dtype) for b in range(n_blocks) for k in (k1, k2)]
         if no_antialias_up:
             # ConvTranspose2d(C, C, 3, s2, p1, op1) == backward-data of conv(3, s2, p1)
             self.up1_up = _pc(S, "up1_up", ConvSpec(c2, c2, 3, 2, 1, PAD_ZERO), dtype)
@@ -679,32 +815,38 @@ class GeneratorEngine:
         self.up1 = _pc(S, "up1_conv.0", ConvSpec(c2 + c1, c1, 3, 1, 1, PAD_ZERO), dtype)
         self.up2 = _pc(S, "up2_conv.0", ConvSpec(c1 + c0, c0, 3, 1, 1, PAD_ZERO), dtype)
         self.outc = _pc(S, "outc.1", ConvSpec(c0, output_nc, 7, 1, 3, PAD_REFLECT), dtype)
-        self.packs = [self.inc, self.down1, self.down2, self.up1, self.up2, self.outc] + \
-            [p for pr in self.res for p in pr] + ([self.up1_up, self.up2_up] if no_antialias_up else [])
+        self.packs = [self.inc, self.down1, self.down2, self.up1, self.up2, self.outc] + res + \
+            ([self.up1_up, self.up2_up] if no_antialias_up else [])
         # fp8 on down2 / up1_conv too (ir:477-482, 557-558): their operands come from the
         # fused resamplers (x1 from down1's Downsample, the up-sampled bottleneck)
         # (their kernels take 128-channel K chunks: down2's Cin = 2*ngf must be a multiple of 128)
         self.fp8_ud = self.fp8 and not no_antialias and not no_antialias_up and c1 % 128 == 0
-        if self.fp8:
-            # weight images 4b..4b+3: conv1 fwd, conv1 dgrad, conv2 fwd, conv2 dgrad of block b;
-            # 4n..4n+3: down2 fwd, down2 dgrad, up1_conv fwd, up1_conv dgrad.
-            # activation slots: forward inputs 2b (conv1), 2b+1 (conv2); backward-data inputs
-            # 2n+2b (conv2's dY), 2n+2b+1 (conv1's dY); 4n: up1_conv's concat [up(h) | x1] (x1
-            # is down2's input: one scale for both), 4n+1 / 4n+2: up1_conv's / down2's dY
-            ud = [self.down2.fwd, self.down2.dg[0][2], self.up1.fwd, self.up1.dg[0][2]] if self.fp8_ud else []
-            self.f8w = ops.Fp8Weights([im for p1, p2 in self.res for im in (p1.fwd, p1.dg[0][2], p2.fwd,
-                                                                             p2.dg[0][2])] + ud, store.device)
-            self.f8a = ops.Fp8Acts(4 * n_blocks + 4, store.device)
-            self.s_cat, self.s_dz3, self.s_dz2 = 4 * n_blocks, 4 * n_blocks + 1, 4 * n_blocks + 2
-            self.s_x1 = 4 * n_blocks + 3   # down2's own x1 copy on the calibration step
-        n_in = 5 + 2 * n_blocks
         # name -> state key of the layer's norm module (the index after its conv)
         nkeys = {"inc": "inc.2", "down1": "down1.1", "down2": "down2.1", "up1": "up1_conv.1", "up2": "up2_conv.1"}
         for b in range(n_blocks):
             nkeys[f"r{b}_1"] = f"resblocks.{b}.conv_block.{k1 + 1}"
             nkeys[f"r{b}_2"] = f"resblocks.{b}.conv_block.{k2 + 1}"
         self.norms = {k: make_norm(norm, S, key) for k, key in nkeys.items()}
-        assert len(self.norms) == n_in
+        assert len(self.norms) == 5 + 2 * n_blocks
+        # the layers fp8_plan knows, as the step names them (GenConv); fp8: each with its record,
+        # and the e4m3 weight images and scale slots numbered by the plan alone
+        recs, self.fp8_slots = fp8_plan(n_blocks, self.fp8_ud) if self.fp8 else ([], {})
+        rec = {r.key: r for r in recs}
+        xp = "xp{j}_{b}" if padding_type == "replicate" else ""
+        convs = [GenConv(self, res[2 * b + j - 1], key, f"r{b}_{j}", "res", rec.get(key), xp=xp.format(j=j, b=b))
+                 for b in range(n_blocks) for j, key in ((1, f"resblocks.{b}.conv_block.{k1}"),
+                                                         (2, f"resblocks.{b}.conv_block.{k2}"))]
+        self.blocks = list(zip(convs[0::2], convs[1::2]))
+        self.c_down2 = GenConv(self, self.down2, "down2.0", "down2", "ud", rec.get("down2.0"), dy8="dz2_8",
+                               s_calib=self.fp8_slots["x1"][0] if self.fp8_ud else None)
+        self.c_up1 = GenConv(self, self.up1, "up1_conv.0", "up1", "ud", rec.get("up1_conv.0"), dy8="dz3_8")
+        if self.fp8:
+            images = [None] * (2 * len(recs))
+            for c in convs + [self.c_down2, self.c_up1]:
+                if c.rec is not None:
+                    images[c.rec.w_fwd], images[c.rec.w_flip] = c.pc.fwd, c.pc.dg[0][2]
+            self.f8w = ops.Fp8Weights(images, store.device)
+            self.f8a = ops.Fp8Acts(sum(n for _, n in self.fp8_slots.values()), store.device)
         self.bufs = Buffers(store.device)
 
     def pack(self):
@@ -714,27 +856,32 @@ class GeneratorEngine:
         if self.fp8:
             self.f8w.run()
 
-    def _w8(self, k):
-        return self.f8w.dst[k], ops.Pi(self.f8w.dq, k)
+    def _fp8_call(self, g: Buffers, B, H, W) -> Fp8Call:
+        """The call's Fp8Call, with the e4m3 operand buffers of the groups that run on fp8: one per
+        ResnetBlock conv input; ``cat1_8`` for up1_conv's concat, whose x1 slice is down2's operand
+        except on the calibration step."""
+        f8, ud = self.fp8_layers(B, H, W)
+        st = Fp8Call(f8, ud, ud and not self.f8a.seen[self.fp8_slots["cat"][0]])
+        H1, W1, H2, W2 = self._dims(H, W)
+        c1, c2, e4m3 = 2 * self.ngf, 4 * self.ngf, torch.float8_e4m3fn
+        if f8:
+            for k, c in enumerate(c for pair in self.blocks for c in pair):
+                st.x8[c.name] = Feat(g.get(f"x8_{k}", (B, H2, W2, c2), e4m3))
+        if ud:
+            st.x8["up1"] = Feat(g.get("cat1_8", (B, H1, W1, c2 + c1), e4m3))
+            st.x8["down2"] = st.x8["up1"].sl(c2, c1)
+        if st.calib:
+            st.x1_8c = Feat(torch.empty((B, H1, W1, c1), dtype=e4m3, device=g.device))
+        return st
 
-    def _res_in(self, g: Buffers, name: str, x: Feat) -> Feat:
-        """A ResnetBlock conv's input as its conv reads it: x itself (reflect: folded into the
-        conv's loads; zero: the conv's own padding), or the ReplicationPad2d(1) copy (kept for
-        the weight gradient)."""
-        if self.padding_type != "replicate":
-            return x
-        xp = Feat(g.get(name, (x.N, x.H + 2, x.W + 2, x.C), self.tdt))
-        ops.pad(x, xp, 1, "replicate")
-        return xp
-
-    def _res_dgrad(self, g: Buffers, pc, dy: Feat, dx: Feat, accumulate, padbuf):
-        """dx (+)= backward-data of a ResnetBlock conv for the padding type."""
-        if self.padding_type != "replicate":
-            ops.conv_dgrad(pc, dy, dx, accumulate=accumulate, pad_buf=padbuf)
-            return
-        dxp = Feat(g.get("res_dxp", (dx.N, dx.H + 2, dx.W + 2, dx.C), self.tdt))
-        ops.conv_dgrad(pc, dy, dxp)
-        ops.pad_fold(dxp, dx, 1, "replicate", accumulate=accumulate)
+    def _fp8_roll(self, st: Fp8Call, group, rng, snapshot=False):
+        """After the last use of the named slot range ``rng`` (fp8_plan) in a pass: the recorded
+        maxima become the next step's scales.  snapshot: first keep the factors just used -- the
+        backward's weight gradients re-read the forward's e4m3 copies with them."""
+        if st.on[group]:
+            if snapshot:
+                self.f8a.snapshot(*self.fp8_slots[rng])
+            self.f8a.update(*self.fp8_slots[rng])
 
     def _bgrad(self, key):
         """Flat-buffer slice of parameter ``key``'s gradient, None when the layout has no
@@ -792,17 +939,8 @@ class GeneratorEngine:
         cat1 = g.get("cat1", (B, H1, W1, c2 + c1), T)     # [up1 out | x1]
         x0 = Feat(cat2, c1, c0)
         x1 = Feat(cat1, c2, c1)
-        f8, ud = self.fp8_layers(B, H, W)
-        g.state["fp8"] = (f8, ud)
-        A = self.f8a if f8 else None
-        cat1_8 = Feat(g.get("cat1_8", (B, H1, W1, c2 + c1), torch.float8_e4m3fn)) if ud else None
-        # first step (current scaling): down2 reads its own copy of x1, scaled from x1 alone,
-        # for its forward AND its weight gradient; up1_conv's concat is then scaled as a whole
-        calib = ud and not A.seen[self.s_cat]
-        g.state["fp8_calib"] = calib
-        x1_8 = Feat(g.get("x1_8c", (B, H1, W1, c1), torch.float8_e4m3fn)) if calib else \
-            (cat1_8.sl(c2, c1) if ud else None)
-        dq_x1 = (A.dqp(self.s_x1) if calib else A.dqp(self.s_cat)) if ud else None
+        st = g.state["fp8"] = self._fp8_call(g, B, H, W)
+        D2, U1 = self.c_down2, self.c_up1
         # inc: reflect-pad 3, conv7x7, IN, ReLU  (ir:458-463)
         z0 = Feat(g.get("z0", (B, H, W, c0), T))
         self.norms["inc"].conv_fwd(g, "inc", self.inc, ir_t, z0, x0, ACT_RELU)   # statistics fused where taken
@@ -814,9 +952,8 @@ class GeneratorEngine:
         else:
             z1 = Feat(g.get("z1", (B, H, W, c1), T))
             self.norms["down1"].resample_fwd(g, "down1", self.down1, x0, z1, "a1", ACT_RELU, x1, ops.blur_down_in,
-                                             ops.blur_down, q8=A.spec(self.s_cat, x1_8) if ud and not calib else None)
-            if calib:
-                A.calibrate(self.s_x1, x1, x1_8)   # down2's operand scaled from x1 alone on the first step
+                                             ops.blur_down, q8=D2.side(st))
+            D2.calibrate(st, x1)   # down2's operand scaled from x1 alone on the first step
         # down2 (+ blur-down)  (ir:477-482)
         h = Feat(g.get("h0", (B, H2, W2, c2), T))
         if self.no_aa:
@@ -825,47 +962,22 @@ class GeneratorEngine:
             self.norms["down2"].fwd(g, "down2", z2, h, ACT_RELU)
         else:
             z2 = Feat(g.get("z2", (B, H1, W1, c2), T))
-            self.norms["down2"].resample_fwd(g, "down2", self.down2, x1, z2, "a2", ACT_RELU, h, ops.blur_down_in,
-                                             ops.blur_down, conv8=(*self._w8(4 * self.n_blocks), x1_8,
-                                                                   dq_x1) if ud else None)
-        # 9 ResnetBlocks  (ir:362-418, 485-490)
-        # fp8: one e4m3 operand buffer, written by the producer of each conv input (the
-        # IN passes, fused; h_0 from blur-down by a quantise launch) and read by the conv
-        # (one buffer per conv input slot: the fp8 weight gradients of the backward read them)
-        x8s = [Feat(g.get(f"x8_{k}", (B, H2, W2, c2), torch.float8_e4m3fn)) for k in range(2 * len(self.res))] \
-            if f8 else None
-        if f8:
-            A.quant(0, h, x8s[0])
-        nres = len(self.res)
-        for b, (p1, p2) in enumerate(self.res):
+            D2.resample_fwd(g, st, x1, z2, "a2", ACT_RELU, h, ops.blur_down_in, ops.blur_down)
+        # 9 ResnetBlocks  (ir:362-418, 485-490); fp8: h_0 (from blur-down) by a quantise launch
+        if self.blocks:
+            self.blocks[0][0].feed(st, h)
+        for b, (ra, rb) in enumerate(self.blocks):
             r1 = Feat(g.get(f"r1_{b}", (B, H2, W2, c2), T))
             t = Feat(g.get(f"t{b}", (B, H2, W2, c2), T))
-            if f8:
-                self.norms[f"r{b}_1"].conv_fwd8(g, f"r{b}_1", p1, *self._w8(4 * b), x8s[2 * b], A.dqp(2 * b), r1, t,
-                                                ACT_RELU, q8=A.spec(2 * b + 1, x8s[2 * b + 1]))
-                A.ensure(2 * b + 1, t, x8s[2 * b + 1])
-            else:
-                self.norms[f"r{b}_1"].conv_fwd(g, f"r{b}_1", p1, self._res_in(g, f"xp1_{b}", h), r1, t, ACT_RELU)
+            ra.fwd(g, st, h, r1, t, ACT_RELU, nxt=rb)
+            if self.use_dropout and train:   # nn.Dropout(0.5) after the ReLU (ir:394-395)
+                t, t1 = Feat(g.get(f"td{b}", (B, H2, W2, c2), T)), t
+                ops.dropout(t1, t, g.state["dropout_seed"] + 2 * b)
             r2 = Feat(g.get(f"r2_{b}", (B, H2, W2, c2), T))
             hn = Feat(g.get(f"h{b + 1}", (B, H2, W2, c2), T))
-            if f8:
-                nxt = 2 * b + 2 if b + 1 < nres else None   # the next block's conv1 input
-                self.norms[f"r{b}_2"].conv_fwd8(g, f"r{b}_2", p2, *self._w8(4 * b + 2), x8s[2 * b + 1],
-                                                A.dqp(2 * b + 1), r2, hn, ACT_NONE, res=h,
-                                                q8=A.spec(nxt, x8s[nxt]) if nxt else None)
-                if nxt:
-                    A.ensure(nxt, hn, x8s[nxt])
-            else:
-                t2 = t
-                if self.use_dropout and train:   # nn.Dropout(0.5) after the ReLU (ir:394-395)
-                    t2 = Feat(g.get(f"td{b}", (B, H2, W2, c2), T))
-                    ops.dropout(t, t2, g.state["dropout_seed"] + 2 * b)
-                self.norms[f"r{b}_2"].conv_fwd(g, f"r{b}_2", p2, self._res_in(g, f"xp2_{b}", t2), r2, hn, ACT_NONE,
-                                               res=h)
+            rb.fwd(g, st, t, r2, hn, ACT_NONE, res=h, nxt=self.blocks[b + 1][0] if b + 1 < self.n_blocks else None)
             h = hn
-        if f8:
-            self.f8a.snapshot(0, 2 * self.n_blocks)  # the scales x8s were made with (fp8 weight gradients)
-            self.f8a.update(0, 2 * self.n_blocks)    # next step's forward scales
+        self._fp8_roll(st, "res", "fwd", snapshot=True)   # next step's forward scales
         # up1 -> cat with x1 -> conv/IN/ReLU  (ir:554-558)
         # (odd sizes: the up-sampled map is 2*H2 x 2*W2 != H1 x W1 and is resized to the
         # skip's size, ir:555-556 -- folded into the UpsampleAA table, or a resize launch
@@ -874,23 +986,19 @@ class GeneratorEngine:
         if self.no_aa_up:
             self._convt(self.up1_up, h, y1, g, "ut1")
         else:
-            ops.upsample(h, y1, q8=A.spec(self.s_cat, cat1_8.sl(0, c2)) if ud and not calib else None)
-        if calib:   # up1_conv's operand scaled from the whole concat on the first step
-            A.calibrate(self.s_cat, Feat(cat1), cat1_8)
+            q8 = U1.side(st, (0, c2))
+            ops.upsample(h, y1, q8=q8 and q8.side)
+        U1.calibrate(st, Feat(cat1))   # up1_conv's operand scaled from the whole concat on the first step
         z3 = Feat(g.get("z3", (B, H1, W1, c1), T))
         # up2 -> cat with x0 -> conv/IN/ReLU  (ir:561-565)
         y2 = Feat(cat2, 0, c1)
         if self.no_aa_up:
             a3 = Feat(g.get("a3", (B, H1, W1, c1), T))   # also the ConvTranspose2d's weight-gradient input
-            self.norms["up1"].conv_fwd(g, "up1", self.up1, Feat(cat1), z3, a3, ACT_RELU)
+            U1.fwd(g, st, Feat(cat1), z3, a3, ACT_RELU)
             self._convt(self.up2_up, a3, y2, g, "ut2")
         else:
-            self.norms["up1"].resample_fwd(g, "up1", self.up1, Feat(cat1), z3, "a3", ACT_RELU, y2, ops.upsample_in,
-                                           ops.upsample, conv8=(*self._w8(4 * self.n_blocks + 2), cat1_8,
-                                                                A.dqp(self.s_cat)) if ud else None)
-        if ud:
-            A.snapshot(self.s_cat, 1)   # the scale cat1_8 was made with (the weight gradients)
-            A.update(self.s_cat, 1)
+            U1.resample_fwd(g, st, Feat(cat1), z3, "a3", ACT_RELU, y2, ops.upsample_in, ops.upsample)
+        self._fp8_roll(st, "ud", "cat", snapshot=True)
         z4 = Feat(g.get("z4", (B, H, W, c0), T))
         a4 = Feat(g.get("a4", (B, H, W, c0), T))
         self.norms["up2"].conv_fwd(g, "up2", self.up2, Feat(cat2), z4, a4, ACT_RELU)
@@ -966,26 +1074,9 @@ class GeneratorEngine:
         else:
             ops.upsample_bwd(dy2, da3)
         # up1_conv
-        f8, ud = g.state.get("fp8", (False, False))
-        A, nb4 = (self.f8a, 4 * self.n_blocks) if f8 else (None, 0)
-        cat1_8 = Feat(g.d["cat1_8"]) if ud else None
-
-        def wg8(pc, key, x8, dqx, dy8, dslot, x, dy):
-            """weight gradient on the fp8 copies (x8 with the scale ``dqx`` it was made with,
-            dy8); bf16 where the kernel does not take the layer"""
-            if not ops.conv_wgrad_fp8(pc.spec, x8, dy8, dqx, A.dqp(dslot), S.krsc(key + ".weight", G)):
-                wg(pc, key, x, dy)
-        da3_8 = Feat(g.get("dz3_8", (B, H1, W1, c1), torch.float8_e4m3fn)) if ud else None
-        self.norms["up1"].bwd(g, "up1", da3, Feat(g.d["z3"]), ACT_RELU, da3, db=self._bgrad("up1_conv.0.bias"),
-                              q8=A.spec(self.s_dz3, da3_8) if ud else None)
+        st = g.state["fp8"]
         dcat1 = Feat(g.get("dcat1", (B, H1, W1, c2 + c1), T))
-        if ud:
-            A.ensure(self.s_dz3, da3, da3_8)
-            wg8(self.up1, "up1_conv.0", cat1_8, A.dqp_used(self.s_cat), da3_8, self.s_dz3, cat1, da3)
-            ops.conv_dgrad_fp8(self.up1, *self._w8(nb4 + 3), da3_8, A.dqp(self.s_dz3), da3, dcat1)
-        else:
-            wg(self.up1, "up1_conv.0", cat1, da3)
-            ops.conv_dgrad(self.up1, da3, dcat1)
+        self.c_up1.bwd(g, st, da3, Feat(g.d["z3"]), ACT_RELU, da3, cat1, dcat1)
         # up1_up
         h9 = Feat(g.d[f"h{self.n_blocks}"])
         dh = Feat(g.get("dh", (B, H2, W2, c2), T))
@@ -997,67 +1088,28 @@ class GeneratorEngine:
         ready("up1_up.weight" if self.no_aa_up else "up1_conv.0.weight")
         # resblocks, reversed: dh holds d h_{b+1}; becomes d h_b in place
         dt_ = Feat(g.get("dtmp", (B, H2, W2, c2), T))
-        nb2 = 2 * self.n_blocks
-        dy8 = Feat(g.get("dy8", (B, H2, W2, c2), torch.float8_e4m3fn)) if f8 else None
-        k1, k2 = self.res_keys
+        dr = Feat(g.get("dtmp2", (B, H2, W2, c2), T))
+        drop = self.use_dropout and "dropout_seed" in g.state
         for b in reversed(range(self.n_blocks)):
-            p1, p2 = self.res[b]
-            key = f"resblocks.{b}.conv_block."
-            t, hb = Feat(g.d[f"t{b}"]), Feat(g.d[f"h{b}"])
-            r1, r2 = Feat(g.d[f"r1_{b}"]), Feat(g.d[f"r2_{b}"])
-            drop = self.use_dropout and "dropout_seed" in g.state
-            # the convs' inputs as they read them: the replicate-padded copies, the dropped-out t
-            t2 = Feat(g.d[f"td{b}"]) if drop else t
-            xin1 = Feat(g.d[f"xp1_{b}"]) if self.padding_type == "replicate" else hb
-            xin2 = Feat(g.d[f"xp2_{b}"]) if self.padding_type == "replicate" else t2
-            s2, s1 = nb2 + 2 * b, nb2 + 2 * b + 1
-            self.norms[f"r{b}_2"].bwd(g, f"r{b}_2", dh, r2, ACT_NONE, dt_, db=self._bgrad(f"{key}{k2}.bias"),
-                                      q8=A.spec(s2, dy8) if f8 else None)
-            dr = Feat(g.get("dtmp2", (B, H2, W2, c2), T))
-            if f8:
-                A.ensure(s2, dt_, dy8)
-                wg8(p2, f"{key}{k2}", Feat(g.d[f"x8_{2 * b + 1}"]), A.dqp_used(2 * b + 1), dy8, s2, xin2, dt_)
-                ops.conv_dgrad_fp8(p2, *self._w8(4 * b + 3), dy8, A.dqp(s2), dt_, dr)
-            else:
-                self._res_dgrad(g, p2, dt_, dr, False, padbuf)
-                wg(p2, f"{key}{k2}", xin2, dt_)
-                if drop:   # backward of the dropout: the same mask and scale on the gradient
-                    ops.dropout(dr, dr, g.state["dropout_seed"] + 2 * b)
-            self.norms[f"r{b}_1"].bwd(g, f"r{b}_1", dr, r1, ACT_RELU, dr, db=self._bgrad(f"{key}{k1}.bias"),
-                                      q8=A.spec(s1, dy8) if f8 else None)
-            if f8:
-                A.ensure(s1, dr, dy8)
-                wg8(p1, f"{key}{k1}", Feat(g.d[f"x8_{2 * b}"]), A.dqp_used(2 * b), dy8, s1, xin1, dr)
-                ops.conv_dgrad_fp8(p1, *self._w8(4 * b + 1), dy8, A.dqp(s1), dr, dh, accumulate=True)
-            else:
-                self._res_dgrad(g, p1, dr, dh, True, padbuf)
-                wg(p1, f"{key}{k1}", xin1, dr)
-            ready(f"{key}{k1}.weight")
-        if f8:
-            self.f8a.update(nb2, nb2)   # next step's backward-data scales
+            ra, rb = self.blocks[b]
+            t = Feat(g.d[f"td{b}"] if drop else g.d[f"t{b}"])   # rb's input: the dropped-out t
+            rb.bwd(g, st, dh, Feat(g.d[f"r2_{b}"]), ACT_NONE, dt_, t, dr, padbuf=padbuf)
+            if drop:   # backward of the dropout: the same mask and scale on the gradient
+                ops.dropout(dr, dr, g.state["dropout_seed"] + 2 * b)
+            ra.bwd(g, st, dr, Feat(g.d[f"r1_{b}"]), ACT_RELU, dr, Feat(g.d[f"h{b}"]), dh, accumulate=True,
+                   padbuf=padbuf)
+            ready(f"{ra.key}.weight")
+        self._fp8_roll(st, "res", "dy")   # next step's backward-data scales
         # down2 (+ blur-down)
-        z2 = Feat(g.d["z2"])
         if self.no_aa:
-            self.norms["down2"].bwd(g, "down2", dh, z2, ACT_RELU, dh, db=self._bgrad("down2.0.bias"))
             dz2 = dh
         else:
             dz2 = Feat(g.get("da2", (B, H1, W1, c2), T))
             ops.blur_down_bwd(dh, dz2)
-            dz2_8 = Feat(g.get("dz2_8", (B, H1, W1, c2), torch.float8_e4m3fn)) if ud else None
-            self.norms["down2"].bwd(g, "down2", dz2, z2, ACT_RELU, dz2, db=self._bgrad("down2.0.bias"),
-                                    q8=A.spec(self.s_dz2, dz2_8) if ud else None)
         dx1 = dcat1.sl(c2, c1)
-        if ud:
-            A.ensure(self.s_dz2, dz2, dz2_8)
-            if g.state.get("fp8_calib"):   # the calibration step's own x1 copy (as its forward read)
-                wg8(self.down2, "down2.0", Feat(g.d.pop("x1_8c")), A.dqp(self.s_x1), dz2_8, self.s_dz2, x1, dz2)
-            else:
-                wg8(self.down2, "down2.0", cat1_8.sl(c2, c1), A.dqp_used(self.s_cat), dz2_8, self.s_dz2, x1, dz2)
-            ops.conv_dgrad_fp8(self.down2, *self._w8(nb4 + 1), dz2_8, A.dqp(self.s_dz2), dz2, dx1, accumulate=True)
-            A.update(self.s_dz3, 2)   # next step's scales of the two dY slots
-        else:
-            wg(self.down2, "down2.0", x1, dz2)
-            ops.conv_dgrad(self.down2, dz2, dx1, accumulate=True)  # x1 feeds down2 and the up1 concat
+        # (accumulated: x1 feeds down2 and the up1 concat)
+        self.c_down2.bwd(g, st, dz2, Feat(g.d["z2"]), ACT_RELU, dz2, x1, dx1, accumulate=True)
+        self._fp8_roll(st, "ud", "ud_dy")   # next step's scales of the two dY slots
         # down1 (+ blur-down)
         z1 = Feat(g.d["z1"])
         if self.no_aa:

@@ -210,6 +210,57 @@ def _desc(**kw):
         return d
 
 
+def _fwd_desc(s: "ConvSpec", x: "Feat", y: "Feat", cin, dtype, out_dtype, act=ACT_NONE, accumulate=0, y_sized=True,
+              **extra):
+    """The forward-style descriptor of conv ``s`` over x (``cin`` channels as stored) with y at the
+    conv's output size (checked, unless y only lends its ld / off: ``y_sized`` False) -- the output
+    of a forward, the dY a weight gradient reads.  ``extra``: the fields that are 0 elsewhere
+    (mask_act / ldm / moff, cin_real, flags)."""
+    N, H, W, ldx = x.t.shape   # one shape read: ~150 conv launches per step go through here
+    Ho, Wo = s.out_hw(H, W)
+    assert not y_sized or y.t.shape[:3] == (N, Ho, Wo), "conv shape mismatch"
+    return _desc(N=N, H=H, W=W, Cin=cin, ldx=ldx, xoff=x.off, Ho=Ho, Wo=Wo, Cout=s.cout, ldy=y.t.shape[3],
+                 yoff=y.off, OH=Ho, OW=Wo, omy=1, ooy=0, omx=1, oox=0, KH=s.k, KW=s.k, sy=s.stride, sx=s.stride,
+                 c0y=-s.pad, c0x=-s.pad, pad_mode=s.mode, act=act, accumulate=int(accumulate), dtype=dtype,
+                 out_dtype=out_dtype, **extra)
+
+
+def _dgrad_desc(pc: "PackedConv", phase, dy: "Feat", dx: "Feat", accumulate, dtype=None, mask: "Feat" = None,
+                mask_act=0, shift=0, **ring):
+    """The backward-data descriptor of one phase (an entry of pc.dg): the stride-1 conv of dy with
+    the phase's flipped image into dx's pixels (py + st * i, px + st * j).  ``shift`` = p: the
+    interior of a reflect-padded layer (the image is packed for the padded domain).  ``dtype``:
+    dy's, when it is not pc's (the e4m3 copy).  ``ring``: fields replaced afterwards -- the
+    split-K ring descriptors of the fp32 path, off the hot path."""
+    (py, _, ay, c0y), (px, _, ax, c0x), _ = phase
+    s, st = pc.spec, pc.spec.stride
+    (N, H, W, ldx), (_, OH, OW, ldy) = dy.t.shape, dx.t.shape
+    d = _desc(N=N, H=H, W=W, Cin=pc.cout_eff, ldx=ldx, xoff=dy.off, Ho=-(-(OH - py) // st),
+              Wo=-(-(OW - px) // st), Cout=s.cin, ldy=ldy, yoff=dx.off, OH=OH, OW=OW, omy=st, ooy=py, omx=st,
+              oox=px, KH=ay, KW=ax, sy=1, sx=1, c0y=c0y + shift, c0x=c0x + shift, pad_mode=PAD_ZERO, act=0,
+              accumulate=int(accumulate), dtype=pc.dtype if dtype is None else dtype, out_dtype=dx.dt,
+              mask_act=mask_act, ldm=mask.ld if mask else 0, moff=mask.off if mask else 0,
+              cin_real=s.cout if s.cout < pc.cout_eff else 0)
+    for k, v in ring.items():
+        setattr(d, k, v)
+    return d
+
+
+IRGAN_EUNSUPPORTED = 1002   # include/irgan.h
+
+
+def _try(name, *args) -> bool:
+    """Call entry point ``name``.  IRGAN_EUNSUPPORTED means the library does not take the
+    arguments and NOTHING ran: False, and the caller takes its other path.  Any other non-zero
+    code raises IrganError naming the entry point."""
+    rc = getattr(_lib.load(), name)(*args)
+    if rc == IRGAN_EUNSUPPORTED:
+        return False
+    if rc != 0:
+        raise _lib.IrganError(f"{name} failed with code {rc}")
+    return True
+
+
 def _rup(a, b):
     return (a + b - 1) // b * b
 
@@ -301,20 +352,14 @@ class PackBatch:
 def conv_fwd(pc: PackedConv, x: Feat, y: Feat, act=ACT_NONE, bias=True, accumulate=False, mask: Feat = None,
              mask_act=0):
     s = pc.spec
-    Ho, Wo = s.out_hw(x.H, x.W)
-    assert (y.H, y.W, y.C) == (Ho, Wo, s.cout) and x.C == pc.cin_eff and y.N == x.N, "conv_fwd shape mismatch"
-    d = _desc(N=x.N, H=x.H, W=x.W, Cin=pc.cin_eff, ldx=x.ld, xoff=x.off, Ho=Ho, Wo=Wo, Cout=s.cout, ldy=y.ld,
-              yoff=y.off, OH=Ho, OW=Wo, omy=1, ooy=0, omx=1, oox=0, KH=s.k, KW=s.k, sy=s.stride, sx=s.stride,
-              c0y=-s.pad, c0x=-s.pad, pad_mode=s.mode, act=act, accumulate=int(accumulate), dtype=pc.dtype,
-              out_dtype=y.dt, mask_act=mask_act, ldm=mask.ld if mask else 0, moff=mask.off if mask else 0,
-              cin_real=s.cin if s.cin < pc.cin_eff else 0)
+    assert y.C == s.cout and x.C == pc.cin_eff, "conv_fwd shape mismatch"
+    d = _fwd_desc(s, x, y, pc.cin_eff, pc.dtype, y.dt, act, accumulate, mask_act=mask_act,
+                  ldm=mask.ld if mask else 0, moff=mask.off if mask else 0,
+                  cin_real=s.cin if s.cin < pc.cin_eff else 0)
     assert x.dt == pc.dtype
     TIMER.wrap(conv_tag("fwd", s, (x.H, x.W), x.N), lambda: _lib.call(
         "irgan_conv_fwd", ctypes.byref(d), x.ptr, P(pc.fwd), P(pc.bias if bias else None), y.ptr,
         mask.ptr if mask else None, stream()))
-
-
-IRGAN_EUNSUPPORTED = 1002   # include/irgan.h
 
 
 def conv_fwd_pool(pc: PackedConv, x: Feat, y, yp: Feat, act=ACT_RELU) -> bool:
@@ -328,18 +373,11 @@ def conv_fwd_pool(pc: PackedConv, x: Feat, y, yp: Feat, act=ACT_RELU) -> bool:
     assert (yp.N, yp.H, yp.W, yp.C) == (x.N, Ho // 2, Wo // 2, s.cout) and x.C == pc.cin_eff
     if y is not None:
         assert (y.H, y.W, y.C, y.N, y.dt) == (Ho, Wo, s.cout, x.N, BF16)
-    d = _desc(N=x.N, H=x.H, W=x.W, Cin=pc.cin_eff, ldx=x.ld, xoff=x.off, Ho=Ho, Wo=Wo, Cout=s.cout,
-              ldy=y.ld if y is not None else s.cout, yoff=y.off if y is not None else 0, OH=Ho, OW=Wo, omy=1, ooy=0,
-              omx=1, oox=0, KH=s.k, KW=s.k, sy=s.stride, sx=s.stride, c0y=-s.pad, c0x=-s.pad, pad_mode=s.mode,
-              act=act, accumulate=0, dtype=pc.dtype, out_dtype=BF16, mask_act=0, ldm=0, moff=0)
-    fn = getattr(_lib.load(), "irgan_conv_fwd_pool")
-    rc = TIMER.wrap(conv_tag("fwdpool", s, (x.H, x.W), x.N), lambda: fn(
-        ctypes.byref(d), x.ptr, P(pc.fwd), P(pc.bias), y.ptr if y is not None else None, yp.ptr, stream()))
-    if rc == IRGAN_EUNSUPPORTED:
-        return False
-    if rc != 0:
-        raise _lib.IrganError(f"irgan_conv_fwd_pool failed with code {rc}")
-    return True
+    # no full-size y: the descriptor carries a dense one's ld / off, which are yp's (checked above)
+    d = _fwd_desc(s, x, y if y is not None else yp, pc.cin_eff, pc.dtype, BF16, act, y_sized=y is not None)
+    return TIMER.wrap(conv_tag("fwdpool", s, (x.H, x.W), x.N), lambda: _try(
+        "irgan_conv_fwd_pool", ctypes.byref(d), x.ptr, P(pc.fwd), P(pc.bias), y.ptr if y is not None else None,
+        yp.ptr, stream()))
 
 
 def conv_fwd_stats(pc: PackedConv, x: Feat, y: Feat, part: torch.Tensor) -> int:
@@ -350,23 +388,13 @@ def conv_fwd_stats(pc: PackedConv, x: Feat, y: Feat, part: torch.Tensor) -> int:
     s = pc.spec
     if pc.dtype != BF16 or y.dt != BF16 or s.cout % 64 or s.cout == 192 or (s.stride != 1 and s.k != 4):
         return 0
-    Ho, Wo = s.out_hw(x.H, x.W)
-    assert (y.H, y.W, y.C) == (Ho, Wo, s.cout) and x.C == pc.cin_eff and y.N == x.N, "conv_fwd shape mismatch"
-    d = _desc(N=x.N, H=x.H, W=x.W, Cin=pc.cin_eff, ldx=x.ld, xoff=x.off, Ho=Ho, Wo=Wo, Cout=s.cout, ldy=y.ld,
-              yoff=y.off, OH=Ho, OW=Wo, omy=1, ooy=0, omx=1, oox=0, KH=s.k, KW=s.k, sy=s.stride, sx=s.stride,
-              c0y=-s.pad, c0x=-s.pad, pad_mode=s.mode, act=ACT_NONE, accumulate=0, dtype=pc.dtype,
-              out_dtype=y.dt, mask_act=0, ldm=0, moff=0, cin_real=s.cin if s.cin < pc.cin_eff else 0)
+    assert y.C == s.cout and x.C == pc.cin_eff, "conv_fwd shape mismatch"
+    d = _fwd_desc(s, x, y, pc.cin_eff, pc.dtype, y.dt, cin_real=s.cin if s.cin < pc.cin_eff else 0)
     nb = ctypes.c_int32(0)
-    fn = getattr(_lib.load(), "irgan_conv_fwd_stats")
-    rc = TIMER.wrap(conv_tag("fwd", s, (x.H, x.W), x.N), lambda: fn(
-        ctypes.byref(d), x.ptr, P(pc.fwd), P(pc.bias), y.ptr, P(part), ctypes.byref(nb), stream()))
-    if rc == IRGAN_EUNSUPPORTED:
-        return 0
-    if rc != 0:
-        raise _lib.IrganError(f"irgan_conv_fwd_stats failed with code {rc}")
-    return int(nb.value)
-
-
+    ran = TIMER.wrap(conv_tag("fwd", s, (x.H, x.W), x.N), lambda: _try(
+        "irgan_conv_fwd_stats", ctypes.byref(d), x.ptr, P(pc.fwd), P(pc.bias), y.ptr, P(part), ctypes.byref(nb),
+        stream()))
+    return int(nb.value) if ran else 0
 
 
 # D's last layer (4x4, stride 1, pad 1, one output channel) on the dedicated VALU kernels
@@ -389,14 +417,9 @@ def patch_head_fwd(pc: PackedConv, x: Feat, y: torch.Tensor) -> bool:
 
     ws = _wgrad_ws(y.device)   # the per-pixel tap products; consumed by the same stream's next launch
 
-    def launch():
-        rc = _lib.load().irgan_patch_head_fwd(x.ptr, x.N, x.H, x.W, x.C, x.ld, x.off, P(pc.fwd),
-                                              P(pc.bias) if pc.bias is not None else None, P(y), P(ws),
-                                              ws.numel(), stream())
-        if rc not in (0, IRGAN_EUNSUPPORTED):
-            raise _lib.IrganError(f"irgan_patch_head_fwd failed with code {rc}")
-        return rc == 0
-    return TIMER.wrap(conv_tag("fwd", pc.spec, (x.H, x.W), x.N), launch)
+    return TIMER.wrap(conv_tag("fwd", pc.spec, (x.H, x.W), x.N), lambda: _try(
+        "irgan_patch_head_fwd", x.ptr, x.N, x.H, x.W, x.C, x.ld, x.off, P(pc.fwd),
+        P(pc.bias) if pc.bias is not None else None, P(y), P(ws), ws.numel(), stream()))
 
 
 def patch_head_dgrad(pc: PackedConv, g: torch.Tensor, dx: Feat) -> bool:
@@ -405,14 +428,9 @@ def patch_head_dgrad(pc: PackedConv, g: torch.Tensor, dx: Feat) -> bool:
     if not is_patch_head(pc, dx):
         return False
     assert g.dtype == torch.float32 and tuple(g.shape[:3]) == (dx.N, dx.H - 1, dx.W - 1) and g.is_contiguous()
-
-    def launch():
-        rc = _lib.load().irgan_patch_head_dgrad(P(g), g.shape[3], P(pc.fwd), dx.ptr, dx.N, dx.H, dx.W, dx.C, dx.ld,
-                                                dx.off, stream())
-        if rc not in (0, IRGAN_EUNSUPPORTED):
-            raise _lib.IrganError(f"irgan_patch_head_dgrad failed with code {rc}")
-        return rc == 0
-    return TIMER.wrap(conv_tag("dgrad", pc.spec, (dx.H, dx.W), dx.N), launch)
+    return TIMER.wrap(conv_tag("dgrad", pc.spec, (dx.H, dx.W), dx.N), lambda: _try(
+        "irgan_patch_head_dgrad", P(g), g.shape[3], P(pc.fwd), dx.ptr, dx.N, dx.H, dx.W, dx.C, dx.ld, dx.off,
+        stream()))
 
 
 def patch_head_wgrad(pc: PackedConv, x: Feat, g: torch.Tensor, dw: torch.Tensor) -> bool:
@@ -424,133 +442,118 @@ def patch_head_wgrad(pc: PackedConv, x: Feat, g: torch.Tensor, dw: torch.Tensor)
     assert g.dtype == torch.float32 and tuple(g.shape[:3]) == (x.N, x.H - 1, x.W - 1) and g.is_contiguous()
     assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == 16 * x.C
     ws = _wgrad_ws(dw.device)
-
-    def launch():
-        rc = _lib.load().irgan_patch_head_wgrad(x.ptr, x.N, x.H, x.W, x.C, x.ld, x.off, P(g), g.shape[3], P(dw),
-                                                P(ws), ws.numel(), stream())
-        if rc not in (0, IRGAN_EUNSUPPORTED):
-            raise _lib.IrganError(f"irgan_patch_head_wgrad failed with code {rc}")
-        return rc == 0
-    return TIMER.wrap(conv_tag("wgrad", pc.spec, (x.H, x.W), x.N), launch)
+    return TIMER.wrap(conv_tag("wgrad", pc.spec, (x.H, x.W), x.N), lambda: _try(
+        "irgan_patch_head_wgrad", x.ptr, x.N, x.H, x.W, x.C, x.ld, x.off, P(g), g.shape[3], P(dw), P(ws),
+        ws.numel(), stream()))
 
 
 def conv_dgrad(pc: PackedConv, dy: Feat, dx: Feat, accumulate=False, mask: Feat = None, mask_act=0,
                pad_buf: torch.Tensor = None, bias=False):
-    """dx = d(conv)/dx^T dy.  Reflect-padded layers: interior straight into dx and the
-    padded ring folded onto dx's border band -- bf16 ResnetBlock shapes: the ring's line
-    GEMM, then the interior launch whose store pass adds the ring terms
-    (irgan_conv_dgrad_reflect_line); other bf16 shapes: the interior launch, then the ring
-    (irgan_reflect_dgrad_ring_ws); fp32: split-K ring partials in pad_buf (fp32 scratch)
-    folded by irgan_reflect_ring_fold; stride-2 layers launch per phase (or all four
-    phases in one irgan_conv_dgrad_s2 launch)."""
+    """dx = d(conv)/dx^T dy.  Reflect-padded layers: _dgrad_reflect; stride-2 layers launch per
+    phase (or all four phases in one irgan_conv_dgrad_s2 launch)."""
     s = pc.spec
     assert dy.C == pc.cout_eff and dx.C == s.cin and dy.dt == pc.dtype
     if pc.reflect:
-        # Backward-data over the reflect-padded domain g (Hp x Wp) folded back:
-        # the interior u in [p, H+p) maps 1:1 onto dx and is written there
-        # directly; only the ring of width p is computed separately.
-        p = s.pad
-        H, W = dx.H, dx.W
-        Hp, Wp = H + 2 * p, W + 2 * p
         assert mask is None
-        (_, _, ay, c0y), (_, _, ax, c0x), buf = pc.dg[0]
-        base = dict(N=dy.N, H=dy.H, W=dy.W, Cin=pc.cout_eff, ldx=dy.ld, xoff=dy.off, Cout=s.cin, KH=ay, KW=ax,
-                    pad_mode=PAD_ZERO, act=0, dtype=pc.dtype, mask_act=0, ldm=0, moff=0,
-                    cin_real=s.cout if s.cout < pc.cout_eff else 0)
-        d = _desc(**base, Ho=H, Wo=W, ldy=dx.ld, yoff=dx.off, OH=H, OW=W, omy=1, ooy=0, omx=1, oox=0, sy=1, sx=1,
-                  c0y=c0y + p, c0x=c0x + p, accumulate=int(accumulate), out_dtype=dx.dt)
+        _dgrad_reflect(pc, dy, dx, accumulate, pad_buf)
+        return
+
+    def phases():
+        if s.stride == 2 and len(pc.dg) == 4 and pc.dtype == BF16 and not bias and _dgrad_s2(pc, dy, dx, accumulate,
+                                                                                              mask, mask_act):
+            return   # all four phases in one launch (irgan_conv_dgrad_s2)
+        for ph in pc.dg:
+            d = _dgrad_desc(pc, ph, dy, dx, accumulate, mask=mask, mask_act=mask_act)
+            if d.Ho <= 0 or d.Wo <= 0:
+                continue
+            assert d.KH > 0 and d.KW > 0
+            _lib.call("irgan_conv_fwd", ctypes.byref(d), dy.ptr, P(ph[2]), P(pc.bias if bias else None), dx.ptr,
+                      mask.ptr if mask else None, stream())
+    TIMER.wrap(conv_tag("dgrad", s, (dx.H, dx.W), dx.N), phases)
+
+
+def _dgrad_reflect(pc: PackedConv, dy: Feat, dx: Feat, accumulate, pad_buf=None, f8=None):
+    """Backward-data of a reflect-padded layer over the padded domain (Hp x Wp) folded back: the
+    interior u in [p, H+p) maps 1:1 onto dx and is written there directly; only the ring of width
+    p is computed separately and folded onto dx's border band.  bf16 ResnetBlock shapes: the
+    ring's line GEMM, then the interior launch whose store pass adds the ring terms
+    (irgan_conv_dgrad_reflect_line[_fp8]); other bf16 shapes: the interior launch, then the ring
+    (irgan_reflect_dgrad_ring_ws); fp32: split-K ring partials in pad_buf (fp32 scratch) folded
+    by irgan_reflect_ring_fold.  f8 = (wd8, dqw, dy8, dqx): the interior on the e4m3 copies of
+    the flipped image and of dy (conv_dgrad_fp8); the ring stays on the bf16 dy."""
+    s, p, H, W = pc.spec, pc.spec.pad, dx.H, dx.W
+    ph = pc.dg[0]
+    (_, _, ay, c0y), (_, _, ax, c0x), buf = ph
+    d = _dgrad_desc(pc, ph, dy, dx, accumulate, shift=p)
+    if f8 is not None:
+        wd8, dqw, dy8, dqx = f8
+        d8 = _dgrad_desc(pc, ph, dy8, dx, accumulate, dtype=FP8, shift=p)
+        ring_mfma = p > 0
+    else:
         ring_mfma = (p > 0 and pc.dtype == BF16 and pc.cout_eff % 32 == 0 and H >= 2 * p + 2
                      and W >= 2 * p + 2 and dy.ld % 8 == 0 and dy.off % 8 == 0)
 
-        def launch():
-            if ring_mfma and RING_LINE[0] and RING_EPI[0] and dx.dt == BF16:
-                # line GEMM, then the interior with the ring folded into its store pass
-                ws = _ring_ws(dx.t.device, dx.N * 4 * 68 * dx.C)
-                rc = _lib.load().irgan_conv_dgrad_reflect_line(ctypes.byref(d), dy.ptr, P(buf), p, dx.ptr, P(ws),
-                                                              ws.numel(), stream())
-                if rc == 0:
-                    return
-                if rc != IRGAN_EUNSUPPORTED:
-                    raise _lib.IrganError(f"irgan_conv_dgrad_reflect_line failed with code {rc}")
+    def launch():
+        if ring_mfma and RING_LINE[0] and RING_EPI[0] and (f8 is not None or dx.dt == BF16):
+            # line GEMM, then the interior with the ring folded into its store pass
+            ws = _ring_ws(dx.t.device, dx.N * 4 * 68 * dx.C)
+            if f8 is None:
+                ran = _try("irgan_conv_dgrad_reflect_line", ctypes.byref(d), dy.ptr, P(buf), p, dx.ptr, P(ws),
+                           ws.numel(), stream())
+            else:
+                ran = _try("irgan_conv_dgrad_reflect_line_fp8", ctypes.byref(d), dy.ptr, P(buf), ctypes.byref(d8),
+                           dy8.ptr, P(wd8), dqx, dqw, p, dx.ptr, P(ws), ws.numel(), stream())
+            if ran:
+                return
+        if f8 is None:
             _lib.call("irgan_conv_fwd", ctypes.byref(d), dy.ptr, P(buf), None, dx.ptr, None, stream())
-            if ring_mfma:
-                _ring(d, dy, buf, p, dx)
+        else:
+            _lib.call("irgan_conv_fwd_fp8", ctypes.byref(d8), dy8.ptr, P(wd8), dqx, dqw, None, dx.ptr, None,
+                      ctypes.byref(ctypes.c_int32(0)), stream())
+        if ring_mfma:
+            _ring(d, dy, buf, p, dx)
 
-        TIMER.wrap(conv_tag("dgrad", s, (H, W), dx.N), launch)
-        if p == 0 or ring_mfma:
-            return
-        # ring in split-K partials: rows[ks][N][2p][Wp][C], cols[ks][N][H][2p][C]
-        rsz, csz = dx.N * 2 * p * Wp * s.cin, dx.N * H * 2 * p * s.cin
-        nk = -(-(ay * ax * pc.cout_eff) // 64)
-        ksplit = 1 if pc.dtype == F32 else max(1, min(nk // 2, 16))
-        assert pad_buf is not None
-        ksplit = max(1, min(ksplit, pad_buf.numel() // (rsz + csz)))
-        rows_b = pad_buf[:ksplit * rsz]
-        cols_b = pad_buf[ksplit * rsz:ksplit * (rsz + csz)]
-        ring = dict(base, ldy=s.cin, yoff=0, accumulate=0, out_dtype=F32)
-        for k in range(p):
-            # padded rows k and H+p+k (full width) -> compact rows k, p+k
-            dr = _desc(**ring, Ho=2, Wo=Wp, OH=2 * p, OW=Wp, omy=p, ooy=k, omx=1, oox=0, sy=H + p, sx=1,
-                       c0y=c0y + k, c0x=c0x)
-            _lib.call("irgan_conv_fwd_splitk", ctypes.byref(dr), dy.ptr, P(buf), P(rows_b), ksplit, rsz, stream())
-            # padded columns k and W+p+k of the interior rows -> compact columns k, p+k
-            dcl = _desc(**ring, Ho=H, Wo=2, OH=H, OW=2 * p, omy=1, ooy=0, omx=p, oox=k, sy=1, sx=W + p,
-                        c0y=c0y + p, c0x=c0x + k)
-            _lib.call("irgan_conv_fwd_splitk", ctypes.byref(dcl), dy.ptr, P(buf), P(cols_b), ksplit, csz, stream())
-        _lib.call("irgan_reflect_ring_fold", P(rows_b), P(cols_b), ksplit, dx.N, H, W, s.cin, p, dx.ptr, dx.dt,
-                  dx.ld, dx.off, stream())
+    TIMER.wrap(conv_tag("dgrad" if f8 is None else "dgrad8", s, (H, W), dx.N), launch)
+    if p == 0 or ring_mfma:
         return
-    st = s.stride
-
-    def phases():
-        if st == 2 and len(pc.dg) == 4 and pc.dtype == BF16 and not bias and _dgrad_s2(pc, dy, dx, accumulate, mask,
-                                                                                        mask_act):
-            return   # all four phases in one launch (irgan_conv_dgrad_s2)
-        for (py, _, ay, c0y), (px, _, ax, c0x), buf in pc.dg:
-            Ho, Wo = -(-(dx.H - py) // st), -(-(dx.W - px) // st)
-            if Ho <= 0 or Wo <= 0:
-                continue
-            assert ay > 0 and ax > 0
-            d = _desc(N=dy.N, H=dy.H, W=dy.W, Cin=pc.cout_eff, ldx=dy.ld, xoff=dy.off, Ho=Ho, Wo=Wo, Cout=s.cin,
-                      ldy=dx.ld, yoff=dx.off, OH=dx.H, OW=dx.W, omy=st, ooy=py, omx=st, oox=px, KH=ay, KW=ax, sy=1,
-                      sx=1, c0y=c0y, c0x=c0x, pad_mode=PAD_ZERO, act=0, accumulate=int(accumulate), dtype=pc.dtype,
-                      out_dtype=dx.dt, mask_act=mask_act, ldm=mask.ld if mask else 0, moff=mask.off if mask else 0,
-                      cin_real=s.cout if s.cout < pc.cout_eff else 0)
-            _lib.call("irgan_conv_fwd", ctypes.byref(d), dy.ptr, P(buf), P(pc.bias if bias else None), dx.ptr,
-                      mask.ptr if mask else None, stream())
-    TIMER.wrap(conv_tag("dgrad", s, (dx.H, dx.W), dx.N), phases)
+    # ring in split-K partials: rows[ks][N][2p][Wp][C], cols[ks][N][H][2p][C]
+    Wp = W + 2 * p
+    rsz, csz = dx.N * 2 * p * Wp * s.cin, dx.N * H * 2 * p * s.cin
+    nk = -(-(ay * ax * pc.cout_eff) // 64)
+    ksplit = 1 if pc.dtype == F32 else max(1, min(nk // 2, 16))
+    assert pad_buf is not None
+    ksplit = max(1, min(ksplit, pad_buf.numel() // (rsz + csz)))
+    rows_b = pad_buf[:ksplit * rsz]
+    cols_b = pad_buf[ksplit * rsz:ksplit * (rsz + csz)]
+    ring = dict(ldy=s.cin, yoff=0, out_dtype=F32)
+    for k in range(p):
+        # padded rows k and H+p+k (full width) -> compact rows k, p+k
+        dr = _dgrad_desc(pc, ph, dy, dx, 0, **ring, Ho=2, Wo=Wp, OH=2 * p, OW=Wp, omy=p, ooy=k, omx=1, oox=0,
+                         sy=H + p, sx=1, c0y=c0y + k, c0x=c0x)
+        _lib.call("irgan_conv_fwd_splitk", ctypes.byref(dr), dy.ptr, P(buf), P(rows_b), ksplit, rsz, stream())
+        # padded columns k and W+p+k of the interior rows -> compact columns k, p+k
+        dcl = _dgrad_desc(pc, ph, dy, dx, 0, **ring, Ho=H, Wo=2, OH=H, OW=2 * p, omy=1, ooy=0, omx=p, oox=k, sy=1,
+                          sx=W + p, c0y=c0y + p, c0x=c0x + k)
+        _lib.call("irgan_conv_fwd_splitk", ctypes.byref(dcl), dy.ptr, P(buf), P(cols_b), ksplit, csz, stream())
+    _lib.call("irgan_reflect_ring_fold", P(rows_b), P(cols_b), ksplit, dx.N, H, W, s.cin, p, dx.ptr, dx.dt,
+              dx.ld, dx.off, stream())
 
 
 def _dgrad_s2(pc: PackedConv, dy: Feat, dx: Feat, accumulate, mask, mask_act) -> bool:
     """The four phase launches of a 4x4 stride-2 backward-data as one irgan_conv_dgrad_s2
     launch; False (nothing ran) when the library does not take the shapes."""
-    s = pc.spec
     descs, ws = (_lib.ConvDesc * 4)(), (ctypes.c_void_p * 4)()
-    for k, ((py, _, ay, c0y), (px, _, ax, c0x), buf) in enumerate(pc.dg):
-        Ho, Wo = -(-(dx.H - py) // 2), -(-(dx.W - px) // 2)
-        descs[k] = _desc(N=dy.N, H=dy.H, W=dy.W, Cin=pc.cout_eff, ldx=dy.ld, xoff=dy.off, Ho=Ho, Wo=Wo, Cout=s.cin,
-                         ldy=dx.ld, yoff=dx.off, OH=dx.H, OW=dx.W, omy=2, ooy=py, omx=2, oox=px, KH=ay, KW=ax, sy=1,
-                         sx=1, c0y=c0y, c0x=c0x, pad_mode=PAD_ZERO, act=0, accumulate=int(accumulate),
-                         dtype=pc.dtype, out_dtype=dx.dt, mask_act=mask_act, ldm=mask.ld if mask else 0,
-                         moff=mask.off if mask else 0, cin_real=s.cout if s.cout < pc.cout_eff else 0)
-        ws[k] = buf.data_ptr()
-    rc = _lib.load().irgan_conv_dgrad_s2(descs, dy.ptr, ws, dx.ptr, mask.ptr if mask else None, stream())
-    if rc == IRGAN_EUNSUPPORTED:
-        return False
-    if rc != 0:
-        raise _lib.IrganError(f"irgan_conv_dgrad_s2 failed with code {rc}")
-    return True
+    for k, ph in enumerate(pc.dg):
+        descs[k] = _dgrad_desc(pc, ph, dy, dx, accumulate, mask=mask, mask_act=mask_act)
+        ws[k] = ph[2].data_ptr()
+    return _try("irgan_conv_dgrad_s2", descs, dy.ptr, ws, dx.ptr, mask.ptr if mask else None, stream())
 
 
 def conv_wgrad(spec: ConvSpec, x: Feat, dy: Feat, dw: torch.Tensor, dtype: int, splitk=0):
     """dw (fp32 KRSC view, accumulated) += weight gradient of conv(x) given dy."""
-    Ho, Wo = spec.out_hw(x.H, x.W)
-    assert (dy.H, dy.W, dy.C) == (Ho, Wo, spec.cout) and x.C >= spec.cin
+    assert dy.C == spec.cout and x.C >= spec.cin
     assert x.dt == dtype and dy.dt == dtype and dw.dtype == torch.float32
-    d = _desc(N=x.N, H=x.H, W=x.W, Cin=spec.cin, ldx=x.ld, xoff=x.off, Ho=Ho, Wo=Wo, Cout=spec.cout, ldy=dy.ld,
-              yoff=dy.off, OH=Ho, OW=Wo, omy=1, ooy=0, omx=1, oox=0, KH=spec.k, KW=spec.k, sy=spec.stride,
-              sx=spec.stride, c0y=-spec.pad, c0x=-spec.pad, pad_mode=spec.mode, act=0, accumulate=1, dtype=dtype,
-              out_dtype=F32, mask_act=0, ldm=0, moff=0, flags=CONV_DETERMINISTIC if _DET[0] else 0)
+    d = _fwd_desc(spec, x, dy, spec.cin, dtype, F32, accumulate=1, flags=CONV_DETERMINISTIC if _DET[0] else 0)
     ws = _wgrad_ws(dw.device) if dtype == BF16 else None
     TIMER.wrap(conv_tag("wgrad", spec, (x.H, x.W), x.N), lambda: _lib.call(
         "irgan_conv_wgrad_ws", ctypes.byref(d), x.ptr, dy.ptr, P(dw), splitk, P(ws), 0 if ws is None else ws.numel(),
@@ -661,23 +664,15 @@ def in_bwd_onepass(dy: Feat, x: Feat, act: int, mr, red, dx: Feat, dy2: Feat = N
     the library does not support the arguments -- then NOTHING ran and nothing was written."""
     N, HW, C = x.N, x.H * x.W, x.C
     d2 = (dy2.ptr, dy2.dt, dy2.ld, dy2.off) if dy2 is not None else (None, 0, 0, 0)
-    lib = _lib.load()
-    if q8 is not None:
-        y8, qp, ap = q8
-        if not (dy.dt == x.dt == dx.dt == BF16 and (dy2 is None or dy2.dt == BF16)):
-            return False
-        assert y8.dt == FP8 and (y8.N, y8.H, y8.W, y8.C) == (dx.N, dx.H, dx.W, C)
-        rc = lib.irgan_in_bwd_onepass_fp8(dy.ptr, dy.ld, dy.off, d2[0], d2[2], d2[3], x.ptr, x.ld, x.off, act, N, HW,
-                                          C, P(mr), P(red), dx.ptr, dx.ld, dx.off, y8.ptr, y8.ld, y8.off, qp, ap,
-                                          stream())
-    else:
-        rc = lib.irgan_in_bwd_onepass(dy.ptr, dy.dt, dy.ld, dy.off, *d2, x.ptr, x.dt, x.ld, x.off, act, N, HW, C,
-                                      P(mr), P(red), dx.ptr, dx.dt, dx.ld, dx.off, stream())
-    if rc == IRGAN_EUNSUPPORTED:
+    if q8 is None:
+        return _try("irgan_in_bwd_onepass", dy.ptr, dy.dt, dy.ld, dy.off, *d2, x.ptr, x.dt, x.ld, x.off, act, N, HW,
+                    C, P(mr), P(red), dx.ptr, dx.dt, dx.ld, dx.off, stream())
+    y8, qp, ap = q8
+    if not (dy.dt == x.dt == dx.dt == BF16 and (dy2 is None or dy2.dt == BF16)):
         return False
-    if rc != 0:
-        raise _lib.IrganError(f"irgan_in_bwd_onepass failed with code {rc}")
-    return True
+    assert y8.dt == FP8 and (y8.N, y8.H, y8.W, y8.C) == (dx.N, dx.H, dx.W, C)
+    return _try("irgan_in_bwd_onepass_fp8", dy.ptr, dy.ld, dy.off, d2[0], d2[2], d2[3], x.ptr, x.ld, x.off, act, N,
+                HW, C, P(mr), P(red), dx.ptr, dx.ld, dx.off, y8.ptr, y8.ld, y8.off, qp, ap, stream())
 
 
 def in_backward(dy: Feat, x: Feat, act: int, mr, work, red, dx: Feat, db=None, dy2: Feat = None, q8=None):
@@ -918,33 +913,21 @@ def sep_resample_in(z: Feat, mr: torch.Tensor, act, y: Feat, ytab, xtab) -> bool
     the kernel does not take the shapes -- then NOTHING ran."""
     (ty, wy, ry, Ty), (tx, wx, rx, Tx) = ytab, xtab
     assert (ry, rx) == (y.H, y.W) and z.C == y.C and z.N == y.N, "sep_resample_in shape mismatch"
-    rc = getattr(_lib.load(), "irgan_sep_resample_in")(
-        z.ptr, z.dt, z.N, z.H, z.W, z.C, z.ld, z.off, P(mr), act, y.ptr, y.dt, y.H, y.W, y.ld, y.off,
-        P(ty), P(wy), Ty, P(tx), P(wx), Tx, stream())
-    if rc == IRGAN_EUNSUPPORTED:
-        return False
-    if rc != 0:
-        raise _lib.IrganError(f"irgan_sep_resample_in failed with code {rc}")
-    return True
+    return _try("irgan_sep_resample_in", z.ptr, z.dt, z.N, z.H, z.W, z.C, z.ld, z.off, P(mr), act, y.ptr, y.dt, y.H,
+                y.W, y.ld, y.off, P(ty), P(wy), Ty, P(tx), P(wx), Tx, stream())
 
 
 def sep_resample_fp8(x: Feat, mr, act, y: Feat, ytab, xtab, q8) -> bool:
     """sep_resample (mr None) / sep_resample_in (mr: act(IN(x)) on load) into bf16 y that
-    also writes y's e4m3 copy: q8 = (y8 Feat, q pointer, amax pointer) as Fp8Acts.spec()
-    gives it (irgan_sep_resample_fp8).  False when the kernel does not take the shapes --
+    also writes y's e4m3 copy: q8 = (y8 Feat, q pointer, amax pointer), an Fp8Out's
+    ``side`` (irgan_sep_resample_fp8).  False when the kernel does not take the shapes --
     then NOTHING ran."""
     (ty, wy, ry, Ty), (tx, wx, rx, Tx) = ytab, xtab
     y8, qp, ap = q8
     assert (ry, rx) == (y.H, y.W) and x.C == y.C and x.N == y.N, "sep_resample_fp8 shape mismatch"
     assert y8.dt == FP8 and (y8.N, y8.H, y8.W, y8.C) == (y.N, y.H, y.W, y.C)
-    rc = getattr(_lib.load(), "irgan_sep_resample_fp8")(
-        x.ptr, x.dt, x.N, x.H, x.W, x.C, x.ld, x.off, P(mr), act, y.ptr, y.dt, y.H, y.W, y.ld, y.off,
-        P(ty), P(wy), Ty, P(tx), P(wx), Tx, y8.ptr, y8.ld, y8.off, qp, ap, stream())
-    if rc == IRGAN_EUNSUPPORTED:
-        return False
-    if rc != 0:
-        raise _lib.IrganError(f"irgan_sep_resample_fp8 failed with code {rc}")
-    return True
+    return _try("irgan_sep_resample_fp8", x.ptr, x.dt, x.N, x.H, x.W, x.C, x.ld, x.off, P(mr), act, y.ptr, y.dt, y.H,
+                y.W, y.ld, y.off, P(ty), P(wy), Ty, P(tx), P(wx), Tx, y8.ptr, y8.ld, y8.off, qp, ap, stream())
 
 
 def blur_down(x: Feat, y: Feat):
@@ -1205,6 +1188,7 @@ class Fp8Acts:
         self.amax = amax_slots(n, device)
         self.q = torch.ones(n, dtype=torch.float32, device=device)
         self.dq = torch.ones(n, dtype=torch.float32, device=device)
+        self.dq_used = torch.ones_like(self.dq)   # snapshot()
         self.seen = [False] * n
 
     def quant(self, slot, x: Feat, y: Feat):
@@ -1214,16 +1198,6 @@ class Fp8Acts:
             fp8_scale(self.amax, self.q, self.dq, reset=False, start=slot, n=1)
             self.seen[slot] = True
         fp8_quant(x, y, Pi(self.q, slot), amax_ptr(self.amax, slot))
-
-    def spec(self, slot, y: Feat):
-        """The (y8, q, amax) side output for a producer that writes the fp8 copy itself
-        (in_apply / in_backward q8=), or None before the slot is calibrated -- then the
-        caller runs ensure() on the produced tensor."""
-        return (y, Pi(self.q, slot), amax_ptr(self.amax, slot)) if self.seen[slot] else None
-
-    def ensure(self, slot, x: Feat, y: Feat):
-        if not self.seen[slot]:
-            self.quant(slot, x, y)
 
     def calibrate(self, slot, x: Feat, y: Feat):
         """Current scaling of slot from x alone, whatever was recorded before (the slot's
@@ -1240,8 +1214,6 @@ class Fp8Acts:
         update() moves them to the next step's): the weight gradients of the backward read
         the forward's e4m3 copies with them."""
         n = self.dq.numel() - start if n is None else n
-        if not hasattr(self, "dq_used"):
-            self.dq_used = torch.ones_like(self.dq)
         self.dq_used[start:start + n].copy_(self.dq[start:start + n])
 
     def dqp_used(self, slot):
@@ -1251,18 +1223,34 @@ class Fp8Acts:
         fp8_scale(self.amax, self.q, self.dq, reset=True, start=start, n=n)
 
 
+class Fp8Out:
+    """What a producer receives as ``q8``: the e4m3 copy of its output for one Fp8Acts slot.
+    ``side`` is the (y8, q pointer, amax pointer) triple of the ops that write the copy in their
+    own store pass (in_apply, in_backward, the fused resamplers), or None before the slot is
+    calibrated.  The producer calls finish() directly after its launch."""
+    __slots__ = ("acts", "slot", "y8", "side")
+
+    def __init__(self, acts: Fp8Acts, slot, y8: Feat):
+        self.acts, self.slot, self.y8 = acts, slot, y8
+        self.side = (y8, Pi(acts.q, slot), amax_ptr(acts.amax, slot)) if acts.seen[slot] else None
+
+    def finish(self, x: Feat, taken=True):
+        """Quantise x standalone if the side output was not taken: the slot was not calibrated
+        (this calibrates it from x), or the producer ran a launch without the fused copy."""
+        if self.side is None:
+            self.acts.quant(self.slot, x, self.y8)
+        elif not taken:
+            fp8_quant(x, *self.side)
+
+
 def conv_fwd_fp8(pc: PackedConv, w8: torch.Tensor, dqw, x8: Feat, dqx, y: Feat, part: torch.Tensor = None,
                  act=ACT_NONE, bias=True, accumulate=False) -> int:
     """conv_fwd on fp8 operands (irgan_conv_fwd_fp8): x8 e4m3 NHWC, w8 the e4m3 copy
     of pc.fwd; dqx / dqw: pointers to the dequantisation multipliers.  With ``part``
     also the InstanceNorm partials of y; returns their count per image (else 0)."""
     s = pc.spec
-    Ho, Wo = s.out_hw(x8.H, x8.W)
-    assert (y.H, y.W, y.C) == (Ho, Wo, s.cout) and x8.C == s.cin and y.N == x8.N and x8.dt == FP8
-    d = _desc(N=x8.N, H=x8.H, W=x8.W, Cin=s.cin, ldx=x8.ld, xoff=x8.off, Ho=Ho, Wo=Wo, Cout=s.cout, ldy=y.ld,
-              yoff=y.off, OH=Ho, OW=Wo, omy=1, ooy=0, omx=1, oox=0, KH=s.k, KW=s.k, sy=s.stride, sx=s.stride,
-              c0y=-s.pad, c0x=-s.pad, pad_mode=s.mode, act=act, accumulate=int(accumulate), dtype=FP8,
-              out_dtype=y.dt, mask_act=0, ldm=0, moff=0)
+    assert y.C == s.cout and x8.C == s.cin and x8.dt == FP8
+    d = _fwd_desc(s, x8, y, s.cin, FP8, y.dt, act, accumulate)
     nb = ctypes.c_int32(0)
     TIMER.wrap(conv_tag("fwd8", s, (x8.H, x8.W), x8.N), lambda: _lib.call(
         "irgan_conv_fwd_fp8", ctypes.byref(d), x8.ptr, P(w8), dqx, dqw, P(pc.bias if bias else None), y.ptr,
@@ -1274,69 +1262,26 @@ def conv_wgrad_fp8(spec: ConvSpec, x8: Feat, dy8: Feat, dqx, dqdy, dw: torch.Ten
     """dw (fp32 KRSC view, accumulated) += weight gradient of conv(x) given dy, on the fp8
     copies x8 / dy8 with their dequantisation pointers (irgan_conv_wgrad_fp8).  False when
     the kernel does not take the layer -- then NOTHING ran (the caller runs the bf16 conv_wgrad)."""
-    Ho, Wo = spec.out_hw(x8.H, x8.W)
-    assert (dy8.H, dy8.W, dy8.C) == (Ho, Wo, spec.cout) and x8.C == spec.cin and x8.dt == FP8 and dy8.dt == FP8
-    d = _desc(N=x8.N, H=x8.H, W=x8.W, Cin=spec.cin, ldx=x8.ld, xoff=x8.off, Ho=Ho, Wo=Wo, Cout=spec.cout, ldy=dy8.ld,
-              yoff=dy8.off, OH=Ho, OW=Wo, omy=1, ooy=0, omx=1, oox=0, KH=spec.k, KW=spec.k, sy=spec.stride,
-              sx=spec.stride, c0y=-spec.pad, c0x=-spec.pad, pad_mode=spec.mode, act=0, accumulate=1, dtype=FP8,
-              out_dtype=F32, mask_act=0, ldm=0, moff=0, flags=CONV_DETERMINISTIC if _DET[0] else 0)
+    assert dy8.C == spec.cout and x8.C == spec.cin and x8.dt == FP8 and dy8.dt == FP8
+    d = _fwd_desc(spec, x8, dy8, spec.cin, FP8, F32, accumulate=1, flags=CONV_DETERMINISTIC if _DET[0] else 0)
     ws = _wgrad_ws(dw.device)
-    rc = [0]
-
-    def launch():
-        rc[0] = _lib.load().irgan_conv_wgrad_fp8(ctypes.byref(d), x8.ptr, dy8.ptr, dqx, dqdy, P(dw), P(ws), ws.numel(),
-                                                 stream())
-    TIMER.wrap(conv_tag("wgrad8", spec, (x8.H, x8.W), x8.N), launch)
-    if rc[0] == IRGAN_EUNSUPPORTED:
-        return False
-    if rc[0] != 0:
-        raise _lib.IrganError(f"irgan_conv_wgrad_fp8 failed with code {rc[0]}")
-    return True
+    return TIMER.wrap(conv_tag("wgrad8", spec, (x8.H, x8.W), x8.N), lambda: _try(
+        "irgan_conv_wgrad_fp8", ctypes.byref(d), x8.ptr, dy8.ptr, dqx, dqdy, P(dw), P(ws), ws.numel(), stream()))
 
 
 def conv_dgrad_fp8(pc: PackedConv, wd8: torch.Tensor, dqw, dy8: Feat, dqx, dy: Feat, dx: Feat, accumulate=False):
     """Backward-data of a stride-1 3x3 layer on fp8 operands (dy8 = e4m3(dy), wd8 = e4m3
     copy of the flipped image pc.dg[0]).  Reflect padding: the interior on fp8, the padded
-    ring from the bf16 dy by irgan_reflect_dgrad_ring (as conv_dgrad); zero padding (down2 /
-    up1_conv of config 5): the flipped conv alone (irgan_conv_fwd_fp8; dy unused)."""
+    ring from the bf16 dy (_dgrad_reflect, as conv_dgrad); zero padding (down2 / up1_conv of
+    config 5): the flipped conv alone (irgan_conv_fwd_fp8; dy unused)."""
     s = pc.spec
     assert s.stride == 1 and dy8.dt == FP8 and dx.C == s.cin
-    if not pc.reflect:
-        (py, _, ay, c0y), (px, _, ax, c0x), buf = pc.dg[0]
-        assert len(pc.dg) == 1 and (dy8.H, dy8.W, dy8.C) == (dx.H, dx.W, pc.cout_eff)
-        d8 = _desc(N=dy8.N, H=dy8.H, W=dy8.W, Cin=pc.cout_eff, ldx=dy8.ld, xoff=dy8.off, Ho=dx.H, Wo=dx.W,
-                   Cout=s.cin, ldy=dx.ld, yoff=dx.off, OH=dx.H, OW=dx.W, omy=1, ooy=py, omx=1, oox=px, KH=ay, KW=ax,
-                   sy=1, sx=1, c0y=c0y, c0x=c0x, pad_mode=PAD_ZERO, act=0, accumulate=int(accumulate), dtype=FP8,
-                   out_dtype=dx.dt, mask_act=0, ldm=0, moff=0)
-        nb = ctypes.c_int32(0)
-        TIMER.wrap(conv_tag("dgrad8", s, (dx.H, dx.W), dx.N), lambda: _lib.call(
-            "irgan_conv_fwd_fp8", ctypes.byref(d8), dy8.ptr, P(wd8), dqx, dqw, None, dx.ptr, None,
-            ctypes.byref(nb), stream()))
+    if pc.reflect:
+        assert dy.dt == BF16
+        _dgrad_reflect(pc, dy, dx, accumulate, f8=(wd8, dqw, dy8, dqx))
         return
-    assert pc.reflect and dy.dt == BF16
-    p = s.pad
-    H, W = dx.H, dx.W
-    (_, _, ay, c0y), (_, _, ax, c0x), buf = pc.dg[0]
-    base = dict(N=dy.N, H=dy.H, W=dy.W, Cin=pc.cout_eff, Cout=s.cin, KH=ay, KW=ax, pad_mode=PAD_ZERO, act=0,
-                mask_act=0, ldm=0, moff=0, Ho=H, Wo=W, ldy=dx.ld, yoff=dx.off, OH=H, OW=W, omy=1, ooy=0, omx=1,
-                oox=0, sy=1, sx=1, c0y=c0y + p, c0x=c0x + p, accumulate=int(accumulate), out_dtype=dx.dt)
-    d8 = _desc(**base, ldx=dy8.ld, xoff=dy8.off, dtype=FP8)
-    d = _desc(**base, ldx=dy.ld, xoff=dy.off, dtype=BF16)
-    nb = ctypes.c_int32(0)
-
-    def launch():
-        if p > 0 and RING_LINE[0] and RING_EPI[0]:
-            # ring line GEMM (bf16), then the fp8 interior folding it in its store pass
-            ws = _ring_ws(dx.t.device, dx.N * 4 * 68 * dx.C)
-            rc = _lib.load().irgan_conv_dgrad_reflect_line_fp8(ctypes.byref(d), dy.ptr, P(buf), ctypes.byref(d8),
-                                                               dy8.ptr, P(wd8), dqx, dqw, p, dx.ptr, P(ws),
-                                                               ws.numel(), stream())
-            if rc == 0:
-                return
-            if rc != IRGAN_EUNSUPPORTED:
-                raise _lib.IrganError(f"irgan_conv_dgrad_reflect_line_fp8 failed with code {rc}")
-        _lib.call("irgan_conv_fwd_fp8", ctypes.byref(d8), dy8.ptr, P(wd8), dqx, dqw, None, dx.ptr, None,
-                  ctypes.byref(nb), stream())
-        if p > 0:
-            _ring(d, dy, buf, p, dx)
-    TIMER.wrap(conv_tag("dgrad8", s, (H, W), dx.N), launch)
+    assert len(pc.dg) == 1 and (dy8.H, dy8.W, dy8.C) == (dx.H, dx.W, pc.cout_eff)
+    d8 = _dgrad_desc(pc, pc.dg[0], dy8, dx, accumulate, dtype=FP8)
+    TIMER.wrap(conv_tag("dgrad8", s, (dx.H, dx.W), dx.N), lambda: _lib.call(
+        "irgan_conv_fwd_fp8", ctypes.byref(d8), dy8.ptr, P(wd8), dqx, dqw, None, dx.ptr, None,
+        ctypes.byref(ctypes.c_int32(0)), stream()))

@@ -1,10 +1,14 @@
 """Host enqueue time vs GPU time per fused train step (is the step launch-bound?)."""
-import importlib, os, sys, time
+import argparse, importlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 irc = importlib.import_module("infrared-colorization-with-resnet-generator-and-patchgan_amd")
-B, H = 16, 256
-cfg = irc.Config(); cfg.device = "cuda:0"; cfg.batch_size = B; cfg.img_size = H
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "fp32"])
+ap.add_argument("--batch", type=int, default=16)
+args = ap.parse_args()
+B, H = args.batch, 256
+cfg = irc.Config(); cfg.device = "cuda:0"; cfg.batch_size = B; cfg.img_size = H; cfg.compute_dtype = args.dtype
 tr = irc.GANTrainer(cfg)
 tr.netG.store.load(irc.seeded_state(irc.g_param_shapes(), 0), strict=True)
 tr.netD.store.load(irc.seeded_state(irc.d_param_shapes(), 1), strict=True)
@@ -23,7 +27,7 @@ for _ in range(20):
 torch.cuda.synchronize()
 wall = (time.perf_counter() - t0) / 20
 enq.sort()
-print(f"wall/step {wall*1e3:.2f} ms, host enqueue/step median {enq[10]*1e3:.2f} ms min {enq[0]*1e3:.2f}")
+print(f"{args.dtype} B={B}: wall/step {wall*1e3:.2f} ms, host enqueue/step median {enq[10]*1e3:.2f} ms min {enq[0]*1e3:.2f}")
 # GPU-only time: queue 20 steps behind a long sleep kernel so the host is never the bottleneck
 torch.cuda.synchronize()
 torch.cuda._sleep(int(2e9))  # ~1 s of GPU spin: the host enqueues everything meanwhile
