@@ -253,7 +253,14 @@ IRGAN_API int irgan_in_bwd_onepass(const void* dy, int32_t dy_dtype, int32_t ldd
  * write y8 = e4m3(clamp(bf16(y) * q[0], +-448)) (an NHWC fp8 slice) and record
  * max |bf16(y)| into the amax slot (IRGAN_FP8_AMAX_PARTS partials): the producers
  * of the fp8 path's ResnetBlock conv operands, so no separate quantise pass runs.
- * IRGAN_EUNSUPPORTED when C, the strides or offsets are not multiples of 8. */
+ * IRGAN_EUNSUPPORTED when C, the strides or offsets are not multiples of 8.
+ * irgan_in_apply_fp8 for a forward that only reads the scales (eval mode):
+ *   amax == NULL  nothing is recorded: no block maximum, no atomic; y and y8 bytes unchanged.
+ *   y == NULL     y8 alone is written (ldy / yoff unused), the bytes of the full call: the
+ *                 value is still rounded to bf16 before the e4m3 conversion.  With res != NULL
+ *                 this is IRGAN_EINVAL and nothing is written (the residual sum is the next
+ *                 block's residual and is needed in bf16); so it is with amax != NULL (a
+ *                 recording pass keeps its bf16 output for the backward). */
 IRGAN_API int irgan_in_apply_fp8(const void* x, int32_t N, int32_t HW, int32_t C, int32_t ldx, int32_t xoff,
                        const float* mr, int32_t act, const void* res, int32_t ldr, int32_t roff, void* y,
                        int32_t ldy, int32_t yoff, void* y8, int32_t ld8, int32_t off8, const float* q,
@@ -461,6 +468,8 @@ IRGAN_API int irgan_sep_resample_in(const void* in, int32_t in_dtype, int32_t N,
  * accumulate) that also writes y8 = e4m3(clamp(bf16(out) * q[0], +-448)) (an NHWC slice, ld8 /
  * off8) and raises max |bf16(out)| into the amax slot (IRGAN_FP8_AMAX_PARTS partials) -- the
  * bytes irgan_fp8_quant makes from the stored out, with no pass reading it back.
+ * amax == NULL (a forward that only reads the scales): nothing is recorded, out and y8 bytes
+ * unchanged.
  * IRGAN_EUNSUPPORTED (nothing launched) unless the LDS form takes the shapes (8-channel-aligned
  * slices, ld8 / off8 % 8, at most 8 taps per axis). */
 IRGAN_API int irgan_sep_resample_fp8(const void* in, int32_t in_dtype, int32_t N, int32_t Hin, int32_t Win,

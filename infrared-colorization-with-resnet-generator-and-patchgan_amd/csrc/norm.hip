@@ -111,7 +111,11 @@ __global__ __launch_bounds__(TPB) void rows_kernel(Slice X, Slice DY, Slice DY2,
 // One batch at a time: two register batches in flight (U rows each, the next batch's loads
 // issued before the current one is used) measured no faster standalone (tools/norm_bench.py)
 // and -0.5 % on the step on the same box (profiles/r05_s5_nab.txt).
-template <int MODE, int U, bool F8 = false>
+// The eval-mode forms of the fp8 forward apply (F8, MODE 4; irgan_in_apply_fp8): AMAX false
+// records nothing -- no running maximum, no fp8_block_amax, so no atomic and no trailing
+// barrier; Y16 false (with AMAX false only) writes the e4m3 copy alone, without the 16-byte bf16
+// store (the value is still rounded to bf16 first, so the bytes are those of the full call).
+template <int MODE, int U, bool F8 = false, bool AMAX = true, bool Y16 = true>
 __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, int xoff, const bf16_t* dy, int lddy,
                                                     int dyoff, const bf16_t* dy2, int lddy2, int dy2off, int act,
                                                     const float* __restrict__ mr, const float* __restrict__ red,
@@ -206,12 +210,14 @@ __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, in
                         w.y = pk_bf16(o[2], o[3]);
                         w.z = pk_bf16(o[4], o[5]);
                         w.w = pk_bf16(o[6], o[7]);
-                        *(uint4*)(dx + (pb + r + u * L.RP) * lddx + dxoff + c) = w;
+                        if constexpr (Y16) *(uint4*)(dx + (pb + r + u * L.RP) * lddx + dxoff + c) = w;
                         if constexpr (F8) {
                             float vb[8];
                             bf8f(w, vb);
+                            if constexpr (AMAX) {
 #pragma unroll
-                            for (int k = 0; k < 8; ++k) amx = fmaxf(amx, fabsf(vb[k]));
+                                for (int k = 0; k < 8; ++k) amx = fmaxf(amx, fabsf(vb[k]));
+                            }
                             *(uint2*)(q8.p + (pb + r + u * L.RP) * q8.ld + q8.off + c) = pack8_fp8(vb, qs);
                         }
                     }
@@ -230,7 +236,7 @@ __global__ __launch_bounds__(TPB) void rows8_kernel(const bf16_t* x, int ldx, in
             part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);
         });
     }
-    if constexpr (F8) fp8_block_amax(amx, q8.amax, blockIdx.y * gridDim.x + blockIdx.x);
+    if constexpr (F8 && AMAX) fp8_block_amax(amx, q8.amax, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // Rows per thread and rows per load batch (U) of each pass, by key: 0 stats, 1 backward
@@ -262,19 +268,19 @@ struct RowArgs {
 inline const bf16_t* bfp(const Slice& s) { return (const bf16_t*)s.p; }
 
 // rows8_kernel with U = min(the thread's rows, the pass's batch), from the instances 2 / 4 / 8 / 16
-template <int MODE, bool F8, int U>
+template <int MODE, bool F8, int U, bool AMAX = true, bool Y16 = true>
 void rows8_launch(const RowGrid& g, hipStream_t st, const RowArgs& a) {
-    rows8_kernel<MODE, U, F8><<<dim3(g.nb, a.N), TPB, 0, st>>>(
+    rows8_kernel<MODE, U, F8, AMAX, Y16><<<dim3(g.nb, a.N), TPB, 0, st>>>(
         bfp(a.X), a.X.ld, a.X.off, bfp(a.DY), a.DY.ld, a.DY.off, bfp(a.DY2), a.DY2.ld, a.DY2.off, a.act, a.mr, a.red,
         (bf16_t*)a.DX.p, a.DX.ld, a.DX.off, a.HW, a.C, g.rows, a.part, a.q8);
 }
-template <int MODE, bool F8>
+template <int MODE, bool F8, bool AMAX = true, bool Y16 = true>
 void rows8_go(int key, const RowGrid& g, hipStream_t st, const RowArgs& a) {
     const int u = std::min(PASS_U[key], irgan_cdiv(g.rows, g.RP));
-    if (u <= 2) rows8_launch<MODE, F8, 2>(g, st, a);
-    else if (u <= 4) rows8_launch<MODE, F8, 4>(g, st, a);
-    else if (u <= 8) rows8_launch<MODE, F8, 8>(g, st, a);
-    else rows8_launch<MODE, F8, 16>(g, st, a);
+    if (u <= 2) rows8_launch<MODE, F8, 2, AMAX, Y16>(g, st, a);
+    else if (u <= 4) rows8_launch<MODE, F8, 4, AMAX, Y16>(g, st, a);
+    else if (u <= 8) rows8_launch<MODE, F8, 8, AMAX, Y16>(g, st, a);
+    else rows8_launch<MODE, F8, 16, AMAX, Y16>(g, st, a);
 }
 
 // fp64 sum of the nb block partials of each (n, c): one block (FC channels x FS partial
@@ -619,12 +625,15 @@ void onepass_go(const RowArgs& a, hipStream_t st) {
 }
 
 // the forward apply as rows8_kernel<4> (all bf16, 8-channel vectors, no xhat; the residual in
-// a.DY), grid as the other row passes; a.q8.p: also the fp8 copy of y (irgan_in_apply_fp8)
+// a.DY), grid as the other row passes; a.q8.p: also the fp8 copy of y (irgan_in_apply_fp8) --
+// without the amax record when a.q8.amax is null, and then alone when a.DX.p is null too
 void apply_rows(const RowArgs& a, hipStream_t st) {
     const int key = a.DY.p || a.q8.p ? 5 : 4;  // 5: apply + residual, or with the fp8 copy
     const RowGrid g = pass_grid(key, a.N, a.HW, a.C, V);
-    if (a.q8.p) rows8_go<4, true>(key, g, st, a);
-    else rows8_go<4, false>(key, g, st, a);
+    if (!a.q8.p) rows8_go<4, false>(key, g, st, a);
+    else if (a.q8.amax && a.DX.p) rows8_go<4, true>(key, g, st, a);
+    else if (a.DX.p) rows8_go<4, true, false, true>(key, g, st, a);
+    else rows8_go<4, true, false, false>(key, g, st, a);
 }
 
 // db[c] += sum of the nb partials' .x, in lane_combine's order (deterministic)
@@ -824,7 +833,10 @@ extern "C" int irgan_in_apply_fp8(const void* x, int32_t N, int32_t HW, int32_t 
                                   const float* mr, int32_t act, const void* res, int32_t ldr, int32_t roff, void* y,
                                   int32_t ldy, int32_t yoff, void* y8, int32_t ld8, int32_t off8, const float* q,
                                   uint32_t* amax, irgan_stream_t s) {
-    if (!x || !mr || !y || !y8 || !q || !amax) return IRGAN_EINVAL;
+    // amax NULL: nothing is recorded; y NULL: y8 alone -- only without the record (the eval-mode
+    // forward's call) and without a residual (the sum is the next block's residual, needed in bf16)
+    if (!x || !mr || !y8 || !q || (!y && (res || amax))) return IRGAN_EINVAL;
+    if (!y) ldy = ld8, yoff = off8;   // unused: pass the checks below
     if (!vec_ok(C, {ldx, xoff, ldy, yoff, ld8, off8}) || (res && !vec_ok(C, {ldr, roff}))) return IRGAN_EUNSUPPORTED;
     if ((long)N * HW * C <= 0) return 0;
     RowArgs a{};

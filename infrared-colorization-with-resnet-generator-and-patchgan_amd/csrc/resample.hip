@@ -119,7 +119,8 @@ __global__ __launch_bounds__(TPB) void sep_kernel(const void* __restrict__ in, i
 // e4m3(clamp(bf16(out) * q8[0], +-448))) with max |bf16(out)| raised into the amax slot --
 // the fp8 path's producers of the down2 / up1_conv operands (x1 from down1's Downsample, the
 // up-sampled bottleneck from UpsampleAA: the two halves of up1_conv's concat), so no separate
-// quantise pass reads them back.
+// quantise pass reads them back.  AMAX false (q8.amax NULL, an eval-mode forward): the same
+// out and o8 bytes with nothing recorded -- no running maximum, no atomic, no trailing barrier.
 struct ResQ8 {
     uint8_t* p;
     int ld, off;
@@ -127,7 +128,7 @@ struct ResQ8 {
     uint32_t* amax;
 };
 constexpr int LTPB = 1024;
-template <int TM, bool NORM = false, int NT = LTPB, bool Q8 = false>
+template <int TM, bool NORM = false, int NT = LTPB, bool Q8 = false, bool AMAX = true>
 __global__ __launch_bounds__(NT) void sep_lds_kernel(const void* __restrict__ in, int idt, int Hin, int Win,
                                                        int ldi, int offi, void* __restrict__ out, int odt, int Hout,
                                                        int Wout, int ldo, int offo, const int* __restrict__ ty,
@@ -232,15 +233,17 @@ __global__ __launch_bounds__(NT) void sep_lds_kernel(const void* __restrict__ in
                 vb[2 * k] = __uint_as_float(wd[k] << 16);
                 vb[2 * k + 1] = __uint_as_float(wd[k] & 0xffff0000u);
             }
+            if constexpr (AMAX) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) amx = fmaxf(amx, fabsf(vb[k]));
+                for (int k = 0; k < 8; ++k) amx = fmaxf(amx, fabsf(vb[k]));
+            }
             const long o8 = (((long)n * Hout + oy) * Wout + ox) * q8.ld + q8.off + c0 + g * 8;
             *(uint2*)(q8.p + o8) = pack8_fp8(vb, qs);
         } else {
             stvec<8>(out, odt, o, acc);
         }
     }
-    if constexpr (Q8) fp8_block_amax(amx, q8.amax, blockIdx.y * gridDim.x + blockIdx.x);
+    if constexpr (Q8 && AMAX) fp8_block_amax(amx, q8.amax, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // Round 6: sep_lds_kernel's map with R output rows per block and the next row's vertical
@@ -263,7 +266,7 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 int sep_swz();
 
-template <int TM, bool NORM, bool Q8, int IPT, int OPT>
+template <int TM, bool NORM, bool Q8, int IPT, int OPT, bool AMAX = true>
 __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict__ in, int Hin, int Win, int ldi,
                                                        int offi, bf16_t* __restrict__ out, int Hout, int Wout,
                                                        int ldo, int offo, const int* __restrict__ ty,
@@ -416,9 +419,11 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
                     vb[2 * q] = __uint_as_float(wd[q] << 16);
                     vb[2 * q + 1] = __uint_as_float(wd[q] & 0xffff0000u);
                 }
-                if (okv) {
+                if constexpr (AMAX) {
+                    if (okv) {
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) amx = fmaxf(amx, fabsf(vb[q]));
+                        for (int q = 0; q < 8; ++q) amx = fmaxf(amx, fabsf(vb[q]));
+                    }
                 }
                 const uint2 p8 = pack8_fp8(vb, qs);
                 const long o8 = (((long)n * Hout + oy) * Wout + ox) * q8.ld + q8.off + c0 + g * 8;
@@ -427,7 +432,7 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
             }
         }
     }
-    if constexpr (Q8) fp8_block_amax(amx, q8.amax, blockIdx.x);
+    if constexpr (Q8 && AMAX) fp8_block_amax(amx, q8.amax, blockIdx.x);
 }
 
 // the pipelined form for a (bf16 -> bf16, no accumulate) resample, or false (nothing launched)
@@ -464,10 +469,10 @@ bool sep_pipe_launch(const void* in, int in_dtype, int N, int Hin, int Win, int 
     const dim3 g(N * irgan_cdiv(Hout, R) * (C / CB));
     const ResQ8 qq = q8 ? *q8 : ResQ8{};
     const int swz = sep_swz();
-#define SPK(TMV, NORMV, Q8V, IP, OP)                                                                               \
-    sep_pipe_kernel<TMV, NORMV, Q8V, IP, OP><<<g, 512, sh, st>>>((const bf16_t*)in, Hin, Win, ldi, offi,          \
-                                                                 (bf16_t*)out, Hout, Wout, ldo, offo, ty, wy, Ty, \
-                                                                 tx, wx, Tx, CB, CBP, R, mr, C, act, swz, qq)
+#define SPK(TMV, NORMV, Q8V, IP, OP)                                                                     \
+    sep_pipe_kernel<TMV, NORMV, (Q8V) != 0, IP, OP, (Q8V) != 2><<<g, 512, sh, st>>>(                       \
+        (const bf16_t*)in, Hin, Win, ldi, offi, (bf16_t*)out, Hout, Wout, ldo, offo, ty, wy, Ty, tx, wx, Tx, \
+        CB, CBP, R, mr, C, act, swz, qq)
 #define SPO(TMV, NORMV, Q8V, IP)                              \
     if (opt == 1) SPK(TMV, NORMV, Q8V, IP, 1);                \
     else if (opt == 2) SPK(TMV, NORMV, Q8V, IP, 2);           \
@@ -479,10 +484,14 @@ bool sep_pipe_launch(const void* in, int in_dtype, int N, int Hin, int Win, int 
     else if (TM <= 4) { SPI(4, NORMV, Q8V) }                  \
     else if (TM <= 6) { SPI(6, NORMV, Q8V) }                  \
     else { SPI(8, NORMV, Q8V) }
-    if (mr && q8) { SPT(true, true) }
-    else if (mr) { SPT(true, false) }
-    else if (q8) { SPT(false, true) }
-    else { SPT(false, false) }
+    // Q8V: 0 no e4m3 copy, 1 the copy and its amax record, 2 the copy alone (q8->amax NULL)
+    const int q8v = !q8 ? 0 : (q8->amax ? 1 : 2);
+    if (mr && q8v == 2) { SPT(true, 2) }
+    else if (mr && q8v) { SPT(true, 1) }
+    else if (mr) { SPT(true, 0) }
+    else if (q8v == 2) { SPT(false, 2) }
+    else if (q8v) { SPT(false, 1) }
+    else { SPT(false, 0) }
 #undef SPT
 #undef SPI
 #undef SPO
@@ -962,15 +971,15 @@ extern "C" int irgan_sep_resample_in(const void* in, int32_t in_dtype, int32_t N
 
 // irgan_sep_resample (mr == NULL) / irgan_sep_resample_in (mr: act(IN(in)) on load) into a
 // bf16 out, no accumulate, that also writes out's e4m3 copy y8 (ld8 / off8: an NHWC slice) with
-// the quantisation factor q[0] and raises max |bf16(out)| into the amax slot (the LDS form only:
-// IRGAN_EUNSUPPORTED otherwise, nothing launched)
+// the quantisation factor q[0] and raises max |bf16(out)| into the amax slot -- amax NULL: records
+// nothing, same out and y8 bytes (the LDS form only: IRGAN_EUNSUPPORTED otherwise, nothing launched)
 extern "C" int irgan_sep_resample_fp8(const void* in, int32_t in_dtype, int32_t N, int32_t Hin, int32_t Win,
                                       int32_t C, int32_t ldi, int32_t offi, const float* mr, int32_t act, void* out,
                                       int32_t out_dtype, int32_t Hout, int32_t Wout, int32_t ldo, int32_t offo,
                                       const int32_t* ty, const float* wy, int32_t Ty, const int32_t* tx,
                                       const float* wx, int32_t Tx, void* y8, int32_t ld8, int32_t off8,
                                       const float* q, uint32_t* amax, irgan_stream_t s) {
-    if (!in || !out || !y8 || !q || !amax) return IRGAN_EINVAL;
+    if (!in || !out || !y8 || !q) return IRGAN_EINVAL;
     const bool vec = (C % 8 == 0) && (ldi % 8 == 0) && (offi % 8 == 0) && (ldo % 8 == 0) && (offo % 8 == 0) &&
                      ld8 % 8 == 0 && off8 % 8 == 0;
     if ((long)N * Hout * Wout * C <= 0) return 0;
@@ -991,16 +1000,19 @@ extern "C" int irgan_sep_resample_fp8(const void* in, int32_t in_dtype, int32_t 
     dim3 g(N * Hout, C / CB);
     const size_t sh = (size_t)Win * CB * 4;
     hipStream_t st = (hipStream_t)s;
-#define SEPQ(T, NORMV)                                                                                            \
-    sep_lds_kernel<T, NORMV, 512, true><<<g, 512, sh, st>>>(in, in_dtype, Hin, Win, ldi, offi, out, out_dtype, Hout, \
-                                                            Wout, ldo, offo, ty, wy, Ty, tx, wx, Tx, 0, CB, mr, C,    \
-                                                            act, sep_swz(), q8)
-#define SEPT(NORMV)                  \
-    if (TM <= 2) SEPQ(2, NORMV);     \
-    else if (TM <= 4) SEPQ(4, NORMV); \
-    else if (TM <= 6) SEPQ(6, NORMV); \
-    else SEPQ(8, NORMV);
-    if (mr) { SEPT(true) } else { SEPT(false) }
+#define SEPQ(T, NORMV, AMAXV)                                                                                \
+    sep_lds_kernel<T, NORMV, 512, true, AMAXV><<<g, 512, sh, st>>>(in, in_dtype, Hin, Win, ldi, offi, out,      \
+                                                                   out_dtype, Hout, Wout, ldo, offo, ty, wy, Ty, \
+                                                                   tx, wx, Tx, 0, CB, mr, C, act, sep_swz(), q8)
+#define SEPT(NORMV, AMAXV)                  \
+    if (TM <= 2) SEPQ(2, NORMV, AMAXV);     \
+    else if (TM <= 4) SEPQ(4, NORMV, AMAXV); \
+    else if (TM <= 6) SEPQ(6, NORMV, AMAXV); \
+    else SEPQ(8, NORMV, AMAXV);
+    if (mr && amax) { SEPT(true, true) }
+    else if (mr) { SEPT(true, false) }
+    else if (amax) { SEPT(false, true) }
+    else { SEPT(false, false) }
 #undef SEPT
 #undef SEPQ
     IRGAN_LAUNCH_CHECK();

@@ -636,9 +636,9 @@ class Fp8Conv(NamedTuple):
 def fp8_plan(n_blocks: int, fp8_ud: bool):
     """The fp8 layout of a generator, the one place that numbers it (table: DESIGN.md s.2): a
     record per e4m3 conv -- the two convs of every ResnetBlock, then down2 and up1_conv when
-    ``fp8_ud`` -- and the named (start, count) slot ranges Fp8Acts.snapshot() / update() run
-    over.  down2 and up1_conv share the operand slot: down2 reads the x1 slice of up1_conv's
-    concat.  Pure host arithmetic, no device."""
+    ``fp8_ud`` -- and the named (start, count) slot ranges the per-call snapshot and
+    Fp8Acts.update() run over.  down2 and up1_conv share the operand slot: down2 reads the x1
+    slice of up1_conv's concat.  Pure host arithmetic, no device."""
     n = n_blocks
     k1, k2 = res_conv_keys()   # the fp8 path runs the default ResnetBlock
     convs = []
@@ -662,10 +662,16 @@ class Fp8Call:
     down2 / up1_conv; GeneratorEngine.fp8_layers); ``calib``: the first 'ud' step (current
     scaling): down2 reads its own copy of x1 (``x1_8c``), scaled from x1 alone, for its forward
     AND its weight gradient, and up1_conv's concat is then scaled as a whole; ``x8``: the e4m3
-    operand buffer by layer name, which the weight gradients re-read."""
+    operand buffer by layer name, which the weight gradients re-read; ``dq_used``: the
+    de-quantisation factors this call's forward made those operands with (one per slot, filled by
+    _fp8_roll before the shared slots move on) -- the call's own, so no other forward between
+    this one and its backward can change them; ``frozen``: an eval-mode call, whose forward
+    reads the shared scales and writes none of them (a backward of it treats its dY slots as
+    every backward does)."""
 
-    def __init__(self, on_res, on_ud, calib):
+    def __init__(self, on_res, on_ud, calib, dq_used, frozen=False):
         self.on, self.calib, self.x1_8c, self.x8 = {"res": on_res, "ud": on_ud}, calib, None, {}
+        self.dq_used, self.frozen = dq_used, frozen
 
 
 class GenConv:
@@ -686,11 +692,11 @@ class GenConv:
 
     def _x8(self, st, used=False):
         """The e4m3 operand and the pointer to its dequantisation factor; ``used``: the one it
-        was made with, after the forward moved the slot on (Fp8Acts.snapshot)."""
+        was made with, kept in the call (Fp8Call.dq_used) before the forward moved the slot on."""
         A = self.eng.f8a
         if st.calib and self.s_calib is not None:
             return st.x1_8c, A.dqp(self.s_calib)
-        return st.x8[self.name], (A.dqp_used if used else A.dqp)(self.rec.s_x)
+        return st.x8[self.name], ops.Pi(st.dq_used, self.rec.s_x) if used else A.dqp(self.rec.s_x)
 
     def _conv8(self, st):
         return (*self._w8(self.rec.w_fwd), *self._x8(st)) if st.on[self.group] else None
@@ -698,16 +704,16 @@ class GenConv:
     def feed(self, st, x: Feat):
         """The operand x from a producer without an e4m3 output: a quantise launch."""
         if st.on[self.group]:
-            self.eng.f8a.quant(self.rec.s_x, x, st.x8[self.name])
+            self.eng.f8a.quant(self.rec.s_x, x, st.x8[self.name], record=not st.frozen)
 
     def side(self, st, sl=None):
         """The ``q8`` of the launch that produces this layer's operand (``sl`` = (off, C): the
         channel slice of it that the launch writes); None on a bf16 call and on the calibration
-        step, where calibrate() quantises instead."""
+        step, where calibrate() quantises instead.  A frozen call gets the read-only form."""
         if not st.on[self.group] or (st.calib and self.group == "ud"):
             return None
         x8 = st.x8[self.name]
-        return ops.Fp8Out(self.eng.f8a, self.rec.s_x, x8.sl(*sl) if sl else x8)
+        return ops.Fp8Out(self.eng.f8a, self.rec.s_x, x8.sl(*sl) if sl else x8, record=not st.frozen)
 
     def calibrate(self, st, x: Feat):
         """Calibration step: the operand's scale from x alone, then its quantisation."""
@@ -794,6 +800,7 @@ class GeneratorEngine:
         self.norm_type, self.padding_type, self.use_dropout = norm, padding_type, bool(use_dropout)
         self.dropout_seed, self.dropout_calls = int(dropout_seed), 0
         self.training = True
+        self.fp8_prepasses = 0   # calibration pre-passes eval-mode forwards have run (forward)
         self.bn_sync = None   # BNSync handle of the fused step's forwards (GANStep, Config.sync_bn)
         self.input_nc, self.output_nc, self.n_blocks = input_nc, output_nc, n_blocks
         self.no_aa, self.no_aa_up = no_antialias, no_antialias_up
@@ -856,12 +863,13 @@ class GeneratorEngine:
         if self.fp8:
             self.f8w.run()
 
-    def _fp8_call(self, g: Buffers, B, H, W) -> Fp8Call:
+    def _fp8_call(self, g: Buffers, B, H, W, frozen=False) -> Fp8Call:
         """The call's Fp8Call, with the e4m3 operand buffers of the groups that run on fp8: one per
         ResnetBlock conv input; ``cat1_8`` for up1_conv's concat, whose x1 slice is down2's operand
-        except on the calibration step."""
+        except on the calibration step (never a frozen call: its slots are calibrated before)."""
         f8, ud = self.fp8_layers(B, H, W)
-        st = Fp8Call(f8, ud, ud and not self.f8a.seen[self.fp8_slots["cat"][0]])
+        dq_used = g.get("fp8_dq_used", (len(self.f8a.seen),), torch.float32) if f8 else None
+        st = Fp8Call(f8, ud, ud and not frozen and not self.f8a.seen[self.fp8_slots["cat"][0]], dq_used, frozen)
         H1, W1, H2, W2 = self._dims(H, W)
         c1, c2, e4m3 = 2 * self.ngf, 4 * self.ngf, torch.float8_e4m3fn
         if f8:
@@ -876,12 +884,27 @@ class GeneratorEngine:
 
     def _fp8_roll(self, st: Fp8Call, group, rng, snapshot=False):
         """After the last use of the named slot range ``rng`` (fp8_plan) in a pass: the recorded
-        maxima become the next step's scales.  snapshot: first keep the factors just used -- the
-        backward's weight gradients re-read the forward's e4m3 copies with them."""
+        maxima become the next step's scales.  snapshot: first keep the factors just used in the
+        call -- the backward's weight gradients re-read the forward's e4m3 copies with them.
+        The forward of a frozen call (its ``snapshot`` rolls) keeps its factors and moves nothing;
+        its backward, if one runs, records and rolls the dY slots like any other backward."""
         if st.on[group]:
+            start, n = self.fp8_slots[rng]
             if snapshot:
-                self.f8a.snapshot(*self.fp8_slots[rng])
-            self.f8a.update(*self.fp8_slots[rng])
+                st.dq_used[start:start + n].copy_(self.f8a.dq[start:start + n])
+            if not (snapshot and st.frozen):
+                self.f8a.update(start, n)
+
+    def reset_fp8_scales(self):
+        """Every fp8 scale slot unseen again: the next forward calibrates from its own batch."""
+        if self.fp8:
+            self.f8a.reset()
+
+    def _fp8_needs_calibration(self, B, H, W):
+        """An eval-mode forward of this shape would read a forward slot nothing has calibrated."""
+        res, ud = self.fp8_layers(B, H, W)
+        (f0, fn), cat = self.fp8_slots["fwd"], self.fp8_slots["cat"][0]
+        return (res and not all(self.f8a.seen[f0:f0 + fn])) or (ud and not self.f8a.seen[cat])
 
     def _bgrad(self, key):
         """Flat-buffer slice of parameter ``key``'s gradient, None when the layout has no
@@ -910,7 +933,7 @@ class GeneratorEngine:
         return res, res and self.fp8_ud and ok(H1, W1, c2 + c1)
 
     def forward(self, ir_nchw: torch.Tensor, bufs: Buffers = None, training: bool = None,
-                bn_repeat: int = 1, bn_sync: bool = False) -> torch.Tensor:
+                bn_repeat: int = 1, bn_sync: bool = False, tape: bool = False) -> torch.Tensor:
         """ir (B, input_nc, H, W) fp32 in [-1,1] -> fake NHWC fp32 (B, H, W, 3).
         Activations land in ``bufs`` (default: the engine's own set).  ``training``
         (default: self.training) decides nn.Dropout's and nn.BatchNorm2d's mode (ir:394-395):
@@ -918,10 +941,24 @@ class GeneratorEngine:
         bn_repeat: BatchNorm's running update applied that many times (BNLayer.repeat).
         bn_sync: synchronise the BatchNorm statistics over the engine's ``bn_sync`` handle (if it
         has one; GANStep's forwards) -- every other caller, the module API among them, normalises
-        with the local batch, as nn.BatchNorm2d does under DDP."""
+        with the local batch, as nn.BatchNorm2d does under DDP.
+        fp8: a training-mode call records every operand's amax and rolls the forward scales on
+        (delayed scaling); an eval-mode call (``training`` False) reads the scales and writes
+        nothing -- no producer records, nothing rolls, and the first norm of each ResnetBlock
+        writes its e4m3 output alone (no ``t{b}`` map; ``tape``: the call's backward will run, the
+        module API under autograd, so the bf16 maps it may read are kept).  Its one possible
+        state change comes first: when a forward slot it will read is unseen, a training-mode
+        forward of the same input calibrates the slots (its output is dropped, the maxima it
+        recorded are cleared), so the call returns what every later call on this input returns."""
         B, _, H, W = ir_nchw.shape
         g, T = bufs or self.bufs, self.tdt
         train = self.training if training is None else bool(training)
+        frozen = self.fp8 and not train
+        if frozen and self._fp8_needs_calibration(B, H, W):
+            self.fp8_prepasses += 1
+            self.forward(ir_nchw, bufs=g, training=True)
+            for rng in ("fwd", "cat", "x1"):
+                self.f8a.clear_amax(*self.fp8_slots[rng])
         if self.norm_type == "batch":
             for n in self.norms.values():
                 n.configure(training=train, groups=1, repeat=bn_repeat, sync=self.bn_sync if bn_sync else None)
@@ -939,8 +976,9 @@ class GeneratorEngine:
         cat1 = g.get("cat1", (B, H1, W1, c2 + c1), T)     # [up1 out | x1]
         x0 = Feat(cat2, c1, c0)
         x1 = Feat(cat1, c2, c1)
-        st = g.state["fp8"] = self._fp8_call(g, B, H, W)
+        st = g.state["fp8"] = self._fp8_call(g, B, H, W, frozen)
         D2, U1 = self.c_down2, self.c_up1
+        t8_only = frozen and st.on["res"] and not tape   # conv2 reads t's e4m3 copy alone
         # inc: reflect-pad 3, conv7x7, IN, ReLU  (ir:458-463)
         z0 = Feat(g.get("z0", (B, H, W, c0), T))
         self.norms["inc"].conv_fwd(g, "inc", self.inc, ir_t, z0, x0, ACT_RELU)   # statistics fused where taken
@@ -968,7 +1006,7 @@ class GeneratorEngine:
             self.blocks[0][0].feed(st, h)
         for b, (ra, rb) in enumerate(self.blocks):
             r1 = Feat(g.get(f"r1_{b}", (B, H2, W2, c2), T))
-            t = Feat(g.get(f"t{b}", (B, H2, W2, c2), T))
+            t = None if t8_only else Feat(g.get(f"t{b}", (B, H2, W2, c2), T))
             ra.fwd(g, st, h, r1, t, ACT_RELU, nxt=rb)
             if self.use_dropout and train:   # nn.Dropout(0.5) after the ReLU (ir:394-395)
                 t, t1 = Feat(g.get(f"td{b}", (B, H2, W2, c2), T)), t

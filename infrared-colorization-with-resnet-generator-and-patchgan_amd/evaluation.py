@@ -169,7 +169,7 @@ def run_test(cfg, model=None, log=print):
         model = IRColorizationModel(cfg)
         if cfg.test_G_weights is not None and os.path.isfile(cfg.test_G_weights):
             log(f"Loading generator weights from: {cfg.test_G_weights}")
-            model.load_weights(cfg.test_G_weights)
+            model.load_weights(cfg.test_G_weights, log=log)
         else:
             log("WARNING: cfg.test_G_weights is None or does not exist; "
                 "generator is randomly initialized, results will be meaningless.")

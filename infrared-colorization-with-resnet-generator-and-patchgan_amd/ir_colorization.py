@@ -314,7 +314,7 @@ class _GFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, *params):
         bufs = Buffers(x.device)
-        fake = mod.engine.forward(x.float(), bufs=bufs)
+        fake = mod.engine.forward(x.float(), bufs=bufs, tape=True)
         ctx.mod, ctx.bufs = mod, bufs
         out = torch.empty(fake.shape[0], fake.shape[3], fake.shape[1], fake.shape[2], device=x.device)
         ops.nhwc_to_nchw(Feat(fake), out)
@@ -388,6 +388,19 @@ class ResnetUNetGenerator(_StoreModule):
         out = torch.empty(fake.shape[0], fake.shape[3], fake.shape[1], fake.shape[2], device=x.device)
         ops.nhwc_to_nchw(Feat(fake), out)
         return out, None
+
+    # The fp8 scale state (compute_dtype "fp8": ops.Fp8Acts) is no parameter and no buffer:
+    # state_dict() stays the reference's keys, and the scales travel beside it.
+    def fp8_state_dict(self):
+        """The delayed-scaling state of the fp8 path (q, dq, amax partials, seen) as CPU tensors;
+        None when the generator does not run on fp8."""
+        return self.engine.f8a.state_dict() if self.engine.fp8 else None
+
+    def load_fp8_state_dict(self, sd):
+        """Restores fp8_state_dict(); ValueError when the slot count is another generator's."""
+        if not self.engine.fp8:
+            raise RuntimeError("load_fp8_state_dict: this generator does not run on fp8")
+        self.engine.f8a.load_state_dict(sd)
 
 
 # =============================================================================
@@ -604,6 +617,9 @@ def ssim_loss_torch(img1, img2, window_size=11, size_average=True):
 # 7) Model wrapper (ir:757-796)
 # =============================================================================
 
+FP8_SIDECAR = ".fp8"   # <generator checkpoint> + this: the fp8 scale state (netG.fp8_state_dict())
+
+
 class IRColorizationModel(nn.Module):
     def __init__(self, cfg: Config):
         super().__init__()
@@ -615,13 +631,20 @@ class IRColorizationModel(nn.Module):
                                         device=self.device, compute_dtype=getattr(cfg, "compute_dtype", "bf16"))
         init_net(self.netG, init_type="normal", init_gain=0.02, device=self.device, initialize_weights=True)
 
-    def load_weights(self, path):
-        """Raw state_dict or {'state_dict': ...}, strict=False (ir:781-789)."""
+    def load_weights(self, path, log=print):
+        """Raw state_dict or {'state_dict': ...}, strict=False (ir:781-789).  An fp8 model also
+        loads the scale state train_kaist saved beside the file (``path + ".fp8"``) when it is
+        there, and says so through ``log``: nothing but the name ties that file to the weights,
+        so one left over from another run is applied too.  Without it the
+        first eval-mode batch calibrates the scales."""
         state = torch.load(path, map_location="cpu", weights_only=True)
         if isinstance(state, dict) and "state_dict" in state:
             state = state["state_dict"]
         self.netG.load_state_dict(state, strict=False)
         self.netG.repack()
+        if self.netG.engine.fp8 and os.path.isfile(str(path) + FP8_SIDECAR):
+            self.netG.load_fp8_state_dict(torch.load(str(path) + FP8_SIDECAR, map_location="cpu", weights_only=True))
+            log(f"Loaded fp8 scale state from: {path}{FP8_SIDECAR}")
 
     def forward(self, ir_tensor):
         fake_b, _ = self.netG(ir_tensor)
@@ -698,17 +721,25 @@ class GANTrainer:
 
     # ---- full training state.  The reference checkpoints G only
     # (ir:1708); this adds D, both Adams (torch.optim.Adam.state_dict() layout) and
-    # the LambdaLR position, so an interrupted run resumes bit-exactly.  Under norm='batch'
-    # the networks' entries carry running_mean / running_var / num_batches_tracked too.
+    # the LambdaLR position, so an interrupted run resumes bit-exactly (in deterministic mode;
+    # fp32, bf16 and fp8 alike).  Under norm='batch' the networks' entries carry running_mean /
+    # running_var / num_batches_tracked too.  compute_dtype "fp8" adds the entry "fp8": the
+    # generator's delayed-scaling state (netG.fp8_state_dict()), without which the resumed run
+    # would recalibrate every slot on its first step; the other dtypes' dicts have no such key.
     def state_dict(self):
         c, s = self.cfg, self.core
-        return {"netG": {k: v.detach().cpu().clone() for k, v in self.netG.store.state().items()},
-                "netD": {k: v.detach().cpu().clone() for k, v in self.netD.store.state().items()},
-                "optimizer_G": self.netG.store.adam_state_dict(c.lr_G * s.lr_scale, (c.beta1, c.beta2), 1e-8, c.lr_G),
-                "optimizer_D": self.netD.store.adam_state_dict(c.lr_D * s.lr_scale, (c.beta1, c.beta2), 1e-8, c.lr_D),
-                "epoch_index": self.epoch_index, "lr_scale": s.lr_scale}
+        sd = {"netG": {k: v.detach().cpu().clone() for k, v in self.netG.store.state().items()},
+              "netD": {k: v.detach().cpu().clone() for k, v in self.netD.store.state().items()},
+              "optimizer_G": self.netG.store.adam_state_dict(c.lr_G * s.lr_scale, (c.beta1, c.beta2), 1e-8, c.lr_G),
+              "optimizer_D": self.netD.store.adam_state_dict(c.lr_D * s.lr_scale, (c.beta1, c.beta2), 1e-8, c.lr_D),
+              "epoch_index": self.epoch_index, "lr_scale": s.lr_scale}
+        if self.netG.engine.fp8:
+            sd["fp8"] = self.netG.fp8_state_dict()
+        return sd
 
     def load_state_dict(self, sd):
+        """An fp8 trainer restores the "fp8" entry, or, given a file without one, starts from
+        unseen scale slots; a trainer of another dtype ignores the entry."""
         self.netG.store.load(sd["netG"], strict=True)
         self.netD.store.load(sd["netD"], strict=True)
         self.netG.store.load_adam_state_dict(sd["optimizer_G"])
@@ -717,6 +748,11 @@ class GANTrainer:
         self.core.lr_scale = float(sd["lr_scale"])
         for net in (self.netG, self.netD):
             net.repack()
+        if self.netG.engine.fp8:
+            if "fp8" in sd:
+                self.netG.load_fp8_state_dict(sd["fp8"])
+            else:
+                self.netG.engine.reset_fp8_scales()
 
     def save_checkpoint(self, path):
         torch.save(self.state_dict(), path)
@@ -847,7 +883,7 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
     model = IRColorizationModel(cfg)
     if cfg.init_G_weights is not None and os.path.isfile(cfg.init_G_weights):
         log(f"Initializing generator from: {cfg.init_G_weights}")
-        model.load_weights(cfg.init_G_weights)
+        model.load_weights(cfg.init_G_weights, log=log)
     trainer = GANTrainer(cfg, model=model)
     if trainer_hook is not None:
         trainer_hook(trainer)
@@ -881,17 +917,25 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
         history.append(dict(epoch=epoch, val_l1=val_l1, **avg))
         if rank == 0 and ((epoch % cfg.save_every == 0) or (epoch == cfg.epochs)):
             path = os.path.join(cfg.save_dir, f"netG_epoch_{epoch:03d}.pth")
-            torch.save(_cpu_state(model.netG), path)
+            _save_generator(model.netG, path)
             log(f"Saved generator checkpoint to {path}")
         if val_l1 < best_val:
             best_val = val_l1
             if rank == 0:
-                torch.save(_cpu_state(model.netG), best_path)
+                _save_generator(model.netG, best_path)
             log(f"New best model saved to {best_path} (val L1={best_val:.4f})")
         trainer.scheduler_step()
         log(f"Current LR (G): {trainer.current_lr_G:.6e}")
     log(f"Training finished. Best val L1: {best_val:.4f}, best model: {best_path}")
     return history
+
+
+def _save_generator(netG, path):
+    """The generator checkpoint in the reference's layout and, for an fp8 generator, its scale
+    state beside it (``path + ".fp8"``, which IRColorizationModel.load_weights picks up)."""
+    torch.save(_cpu_state(netG), path)
+    if netG.engine.fp8:
+        torch.save(netG.fp8_state_dict(), path + FP8_SIDECAR)
 
 
 def _cpu_state(net):

@@ -591,14 +591,21 @@ def in_finalize(x: Feat, part: torch.Tensor, nb: int, mr: torch.Tensor):
 
 def in_apply(x: Feat, mr, y: Feat, act=ACT_NONE, res: Feat = None, xhat: torch.Tensor = None, q8=None):
     """y = act(IN(x)) [+ res].  q8 = (y8 Feat, q ptr, amax ptr): also the fp8 copy of y
-    (irgan_in_apply_fp8; bf16, no xhat)."""
-    assert x.dt == y.dt
+    (irgan_in_apply_fp8; bf16, no xhat).  The amax pointer may be None (nothing recorded), and
+    then, without a residual, so may y: the e4m3 copy alone, for a forward whose bf16 y nobody
+    reads."""
+    assert y is not None or (q8 is not None and q8[2] is None and res is None)
+    assert y is None or x.dt == y.dt
     if q8 is not None:
         y8, qp, ap = q8
-        assert xhat is None and x.dt == BF16 and y8.dt == FP8 and (y8.N, y8.H, y8.W, y8.C) == (y.N, y.H, y.W, y.C)
-        _lib.call("irgan_in_apply_fp8", x.ptr, x.N, x.H * x.W, x.C, x.ld, x.off, P(mr), act,
-                  res.ptr if res else None, res.ld if res else 0, res.off if res else 0, y.ptr, y.ld, y.off,
-                  y8.ptr, y8.ld, y8.off, qp, ap, stream())
+        assert xhat is None and x.dt == BF16 and y8.dt == FP8 and (y8.N, y8.H, y8.W, y8.C) == (x.N, x.H, x.W, x.C)
+        assert y is None or (y.N, y.H, y.W, y.C) == (x.N, x.H, x.W, x.C)
+        kind = "in_apply8_res" if res is not None else ("in_apply8" if y is not None else "in_apply8_only")
+        _timed(kind, x, lambda: _lib.call(
+            "irgan_in_apply_fp8", x.ptr, x.N, x.H * x.W, x.C, x.ld, x.off, P(mr), act,
+            res.ptr if res else None, res.ld if res else 0, res.off if res else 0,
+            y.ptr if y is not None else None, y.ld if y is not None else 0, y.off if y is not None else 0,
+            y8.ptr, y8.ld, y8.off, qp, ap, stream()))
         return
     _timed("in_apply_res" if res is not None else "in_apply", x, lambda: _lib.call(
         "irgan_in_apply", x.ptr, x.dt, x.N, x.H * x.W, x.C, x.ld, x.off, P(mr), act, res.ptr if res else None,
@@ -919,8 +926,8 @@ def sep_resample_in(z: Feat, mr: torch.Tensor, act, y: Feat, ytab, xtab) -> bool
 
 def sep_resample_fp8(x: Feat, mr, act, y: Feat, ytab, xtab, q8) -> bool:
     """sep_resample (mr None) / sep_resample_in (mr: act(IN(x)) on load) into bf16 y that
-    also writes y's e4m3 copy: q8 = (y8 Feat, q pointer, amax pointer), an Fp8Out's
-    ``side`` (irgan_sep_resample_fp8).  False when the kernel does not take the shapes --
+    also writes y's e4m3 copy: q8 = (y8 Feat, q pointer, amax pointer or None: nothing
+    recorded), an Fp8Out's ``side`` (irgan_sep_resample_fp8).  False when the kernel does not take the shapes --
     then NOTHING ran."""
     (ty, wy, ry, Ty), (tx, wx, rx, Tx) = ytab, xtab
     y8, qp, ap = q8
@@ -1182,17 +1189,24 @@ class Fp8Acts:
     """Per-tensor scales of fp8 activation operands with delayed scaling: a slot's
     tensor is quantised with the q made from the amax it had at the previous step
     (its first use calibrates from its own amax).  update() turns the recorded maxima
-    into the next step's q / dq."""
+    into the next step's q / dq.  A slot is unseen (``seen`` False: its next use calibrates it),
+    delayed (a training pass records its amax and update() moves its scale) or, for an eval-mode
+    forward, frozen: read with ``record=False`` / an Fp8Out(record=False), never written.
+    The tensors are allocated once and only ever changed in place, so a Pi() pointer into them
+    stays valid across reset() and load_state_dict()."""
 
     def __init__(self, n, device):
         self.amax = amax_slots(n, device)
         self.q = torch.ones(n, dtype=torch.float32, device=device)
         self.dq = torch.ones(n, dtype=torch.float32, device=device)
-        self.dq_used = torch.ones_like(self.dq)   # snapshot()
         self.seen = [False] * n
 
-    def quant(self, slot, x: Feat, y: Feat):
-        """Standalone quantisation of x into y (irgan_fp8_quant)."""
+    def quant(self, slot, x: Feat, y: Feat, record=True):
+        """Standalone quantisation of x into y (irgan_fp8_quant).  record False: with the slot's
+        scale as it stands, nothing written to the slot."""
+        if not record:
+            fp8_quant(x, y, Pi(self.q, slot), None)
+            return
         if not self.seen[slot]:
             fp8_quant(x, None, None, amax_ptr(self.amax, slot))
             fp8_scale(self.amax, self.q, self.dq, reset=False, start=slot, n=1)
@@ -1202,37 +1216,61 @@ class Fp8Acts:
     def calibrate(self, slot, x: Feat, y: Feat):
         """Current scaling of slot from x alone, whatever was recorded before (the slot's
         partial maxima are cleared first), then the quantisation of x into y."""
-        self.amax[slot * FP8_AMAX_PARTS:(slot + 1) * FP8_AMAX_PARTS].zero_()
+        self.clear_amax(slot, 1)
         self.seen[slot] = False
         self.quant(slot, x, y)
 
     def dqp(self, slot):
         return Pi(self.dq, slot)
 
-    def snapshot(self, start=0, n=None):
-        """Keep the dequantisation factors slots [start, start+n) were just used with (before
-        update() moves them to the next step's): the weight gradients of the backward read
-        the forward's e4m3 copies with them."""
-        n = self.dq.numel() - start if n is None else n
-        self.dq_used[start:start + n].copy_(self.dq[start:start + n])
-
-    def dqp_used(self, slot):
-        return Pi(self.dq_used, slot)
-
     def update(self, start=0, n=None):
         fp8_scale(self.amax, self.q, self.dq, reset=True, start=start, n=n)
+
+    def clear_amax(self, start=0, n=None):
+        """Forget the maxima recorded in slots [start, start+n)."""
+        n = self.q.numel() - start if n is None else n
+        self.amax[start * FP8_AMAX_PARTS:(start + n) * FP8_AMAX_PARTS].zero_()
+
+    def reset(self):
+        """Every slot unseen, as constructed (in place)."""
+        self.amax.zero_()
+        self.q.fill_(1.0)
+        self.dq.fill_(1.0)
+        self.seen[:] = [False] * len(self.seen)
+
+    def state_dict(self):
+        """q, dq, the amax partials and seen as CPU tensors (torch.load(weights_only=True) takes
+        them)."""
+        return {"q": self.q.detach().cpu().clone(), "dq": self.dq.detach().cpu().clone(),
+                "amax": self.amax.detach().cpu().clone(), "seen": torch.tensor(self.seen, dtype=torch.bool)}
+
+    def load_state_dict(self, sd):
+        """Copies a state_dict() into the slots in place (the pointers handed out stay valid)."""
+        have, want = len(self.seen), int(sd["seen"].numel())
+        if want != have or sd["q"].numel() != have or sd["dq"].numel() != have or \
+                sd["amax"].numel() != have * FP8_AMAX_PARTS:
+            raise ValueError(f"fp8 scale state of {want} slots does not fit this generator's {have} slots")
+        self.q.copy_(sd["q"].to(torch.float32))
+        self.dq.copy_(sd["dq"].to(torch.float32))
+        self.amax.copy_(sd["amax"].to(torch.int32))
+        self.seen[:] = [bool(v) for v in sd["seen"].tolist()]
 
 
 class Fp8Out:
     """What a producer receives as ``q8``: the e4m3 copy of its output for one Fp8Acts slot.
     ``side`` is the (y8, q pointer, amax pointer) triple of the ops that write the copy in their
     own store pass (in_apply, in_backward, the fused resamplers), or None before the slot is
-    calibrated.  The producer calls finish() directly after its launch."""
-    __slots__ = ("acts", "slot", "y8", "side")
+    calibrated.  The producer calls finish() directly after its launch.
+    record False (an eval-mode forward): the read-only form, side = (y8, q pointer, None) --
+    the slot's scale as it stands, and finish() never falls back to a recording quantise."""
+    __slots__ = ("acts", "slot", "y8", "side", "record")
 
-    def __init__(self, acts: Fp8Acts, slot, y8: Feat):
-        self.acts, self.slot, self.y8 = acts, slot, y8
-        self.side = (y8, Pi(acts.q, slot), amax_ptr(acts.amax, slot)) if acts.seen[slot] else None
+    def __init__(self, acts: Fp8Acts, slot, y8: Feat, record=True):
+        self.acts, self.slot, self.y8, self.record = acts, slot, y8, record
+        if record:
+            self.side = (y8, Pi(acts.q, slot), amax_ptr(acts.amax, slot)) if acts.seen[slot] else None
+        else:
+            self.side = (y8, Pi(acts.q, slot), None)
 
     def finish(self, x: Feat, taken=True):
         """Quantise x standalone if the side output was not taken: the slot was not calibrated
