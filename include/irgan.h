@@ -592,6 +592,17 @@ IRGAN_API int irgan_linear_area_resize_u8(const void* src, int32_t N, int32_t Hi
  * images whose img_max[n] <= 1 are not divided by 255. */
 IRGAN_API int irgan_u8_to_unit(const void* in, int32_t N, int64_t per_image, const int32_t* img_max, int32_t max_rule,
                      float* out, irgan_stream_t s);
+/* img_size=None, or a target equal to the source size: the loaders skip cv2.resize
+ * (ir:817-818, 847-848) and OpenCV copies when dsize == ssize.  src uint8 [N][H][W][C]
+ * (C <= 4, image stride img_stride bytes) -> out float32 [N][C][H][W] in [-1, 1] with
+ * irgan_u8_to_unit's arithmetic (bit-identical to irgan_area_resize_u8 with identity
+ * tables + irgan_u8_to_unit), in one launch.  flip as irgan_area_resize_u8.
+ * max_rule = 1: the IR rule of ir:1142, with a max pass over img_max (zeroed int32 per
+ * image, required) before the convert pass; max_rule = 0: img_max is not read.
+ * out_u8 (nullable): the flipped bytes as uint8 [N][C][H][W]. */
+IRGAN_API int irgan_u8_native_to_unit(const void* src, int32_t N, int32_t H, int32_t W, int32_t C, int64_t img_stride,
+                            const void* flip, int32_t max_rule, int32_t* img_max, float* out, void* out_u8,
+                            irgan_stream_t s);
 
 /* The SSIM of compute_metrics (ir:1208-1213): skimage.metrics.structural_similarity(
  * gt, pred, data_range=1.0, channel_axis=2) for N uint8 image pairs [N][H][W][C]

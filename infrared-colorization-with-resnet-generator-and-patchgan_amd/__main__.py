@@ -1,12 +1,27 @@
-"""``python -m infrared-colorization-with-resnet-generator-and-patchgan_amd [train|test]``
--- the reference's script entry point (ir:1730-1756) with cfg.mode taken from
-the command line (default: Config's "test")."""
+"""``python -m infrared-colorization-with-resnet-generator-and-patchgan_amd [train|test]
+[--img-size N | HxW | native]`` -- the reference's script entry point (ir:1730-1756) with
+cfg.mode taken from the command line (default: Config's "test").  ``--img-size`` sets
+cfg.img_size: N for N x N, HxW (height first, e.g. 512x640) or ``native`` for every frame
+at its own size; without the flag Config's value stands."""
+import argparse
 import sys
 
+from .data import parse_img_size
 from .ir_colorization import Config, main
 
-if __name__ == "__main__":
+
+def config_from_argv(argv):
+    ap = argparse.ArgumentParser(prog="python -m infrared-colorization-with-resnet-generator-and-patchgan_amd")
+    ap.add_argument("mode", nargs="?", help="train or test (default: Config.mode)")
+    ap.add_argument("--img-size", type=parse_img_size, default=argparse.SUPPRESS, metavar="N|HxW|native")
+    a = ap.parse_args(argv)
     cfg = Config()
-    if len(sys.argv) > 1:
-        cfg.mode = sys.argv[1]
-    main(cfg)
+    if a.mode is not None:
+        cfg.mode = a.mode
+    if hasattr(a, "img_size"):
+        cfg.img_size = a.img_size
+    return cfg
+
+
+if __name__ == "__main__":
+    main(config_from_argv(sys.argv[1:]))

@@ -20,6 +20,10 @@
 //    resized bytes (IR rule) by one atomicMax per block.
 //  * unit_kernel: uint8 -> float32 [-1, 1]: v / 255 (correctly rounded float32
 //    division, as numpy), then * 2 - 1 (torch float32), the IR max rule applied.
+//  * max_u8_kernel + native_unit_kernel: img_size=None (or a target equal to the
+//    source size), where cv2.resize is skipped (ir:817-818) or copies: uint8 NHWC
+//    -> float32 NCHW [-1, 1] in one pass with unit_kernel's arithmetic, 16-byte
+//    loads and per-plane float4 stores; the IR max rule needs the max pass first.
 // Byte-sized HBM streams; no LDS, no MFMA.
 #include "common.h"
 
@@ -142,6 +146,127 @@ __global__ __launch_bounds__(TPB) void unit_kernel(const uint8_t* __restrict__ i
     }
 }
 
+// The [-1, 1] value of one byte: unit_kernel's arithmetic, op for op.
+IRGAN_HD float unit_value(uint32_t b, bool div) {
+#pragma clang fp contract(off)
+    float v = (float)b;
+    if (div) v = v / 255.0f;
+    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+    return v * 2.0f - 1.0f;
+}
+
+constexpr int RUN = 16;  // pixels per lane of the native kernel: C 16-byte loads, 4 float4 stores per plane
+
+// img_max[n] (zeroed) = max byte of image n: len contiguous bytes at src + n * img_stride.
+// 16-byte loads from the first aligned byte on, the < 16 bytes before and after it one per
+// thread; one atomicMax per wave.
+__global__ __launch_bounds__(TPB) void max_u8_kernel(const uint8_t* __restrict__ src, long len, long img_stride,
+                                                     int* __restrict__ img_max) {
+    const int n = blockIdx.y;
+    const uint8_t* S = src + n * img_stride;
+    const long head = min(len, (long)((16 - ((uintptr_t)S & 15)) & 15));
+    const long nvec = (len - head) >> 4, tail0 = head + (nvec << 4);
+    const long t = blockIdx.x * (long)TPB + threadIdx.x, T = (long)gridDim.x * TPB;
+    uint32_t m = 0;
+    for (long i = t; i < nvec; i += T) {
+        const uint4 v = *(const uint4*)(S + head + (i << 4));
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            m = max(max(m, w[k] & 0xFF), (w[k] >> 8) & 0xFF);
+            m = max(max(m, (w[k] >> 16) & 0xFF), w[k] >> 24);
+        }
+    }
+    if (t < head) m = max(m, (uint32_t)S[t]);
+    if (t < len - tail0) m = max(m, (uint32_t)S[tail0 + t]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(img_max + n, (int)m);
+}
+
+// src: uint8 [N][H][W][C] (image stride img_stride bytes); out: float32 [N][C][H][W] in [-1, 1]
+// (unit_value), out8 (nullable): the same bytes as uint8 [N][C][H][W].  A row is cut into
+// U = cdiv(W, RUN) + 1 units at the first pixel p whose byte address is 16-byte aligned:
+// unit 0 = pixels [0, p), unit u = [p + RUN * (u - 1), p + RUN * u), clipped to the row.
+// One lane = one unit: a whole unit takes C 16-byte loads and, per channel plane, 4 float4
+// stores where the destination run is 16-byte aligned (dword stores otherwise); a clipped
+// unit, or a row with no aligned pixel start (C = 2, 4 on an odd address), goes pixel by
+// pixel.  The flip reverses the destination run: source pixel x lands on column W - 1 - x.
+template <int C>
+__global__ __launch_bounds__(TPB) void native_unit_kernel(const uint8_t* __restrict__ src, int H, int W,
+                                                          long img_stride, int U, const uint8_t* __restrict__ flip,
+                                                          const int* __restrict__ img_max, int max_rule,
+                                                          float* __restrict__ out, uint8_t* __restrict__ out8) {
+    const int n = blockIdx.y;
+    const long e = blockIdx.x * (long)TPB + threadIdx.x;
+    if (e >= (long)H * U) return;
+    const int y = (int)(e / U), u = (int)(e - (long)y * U);
+    const uint8_t* row = src + n * img_stride + (long)y * W * C;
+    int p = -1;
+#pragma unroll
+    for (int k = RUN - 1; k >= 0; --k)
+        if ((((uintptr_t)row + k * C) & 15) == 0) p = k;
+    const bool aligned = p >= 0;
+    if (!aligned) p = 0;
+    const int x0 = p + (u - 1) * RUN, x1 = x0 + RUN;
+    const bool fl = flip && flip[n];
+    const bool div = !max_rule || img_max[n] > 1;
+    const long HW = (long)H * W, o0 = (long)n * C * HW + (long)y * W;
+    if (aligned && x0 >= 0 && x1 <= W) {
+        uint32_t w[4 * C];
+        const uint4* q = (const uint4*)(row + (long)x0 * C);
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const uint4 v = q[k];
+            w[4 * k] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+        }
+        const long od = o0 + (fl ? W - x1 : x0);   // destination run [od, od + RUN) of plane 0
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            uint32_t b[RUN];
+#pragma unroll
+            for (int j = 0; j < RUN; ++j) {
+                const int i0 = j * C + c, i1 = (RUN - 1 - j) * C + c;   // byte of run pixel j, and flipped
+                const uint32_t b0 = (w[i0 >> 2] >> (8 * (i0 & 3))) & 0xFF, b1 = (w[i1 >> 2] >> (8 * (i1 & 3))) & 0xFF;
+                b[j] = fl ? b1 : b0;
+            }
+            float* d = out + od + c * HW;
+            if (((uintptr_t)d & 15) == 0) {
+#pragma unroll
+                for (int j = 0; j < RUN; j += 4)
+                    *(float4*)(d + j) = float4{unit_value(b[j], div), unit_value(b[j + 1], div),
+                                               unit_value(b[j + 2], div), unit_value(b[j + 3], div)};
+            } else {
+#pragma unroll
+                for (int j = 0; j < RUN; ++j) d[j] = unit_value(b[j], div);
+            }
+            if (out8) {
+                uint8_t* d8 = out8 + od + c * HW;
+                if (((uintptr_t)d8 & 15) == 0) {
+                    uint32_t pk[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        pk[j] = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+                    *(uint4*)d8 = uint4{pk[0], pk[1], pk[2], pk[3]};
+                } else {
+#pragma unroll
+                    for (int j = 0; j < RUN; ++j) d8[j] = (uint8_t)b[j];
+                }
+            }
+        }
+        return;
+    }
+    for (int x = max(x0, 0); x < min(x1, W); ++x) {
+        const long od = o0 + (fl ? W - 1 - x : x);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const uint32_t b = row[(long)x * C + c];
+            out[od + c * HW] = unit_value(b, div);
+            if (out8) out8[od + c * HW] = (uint8_t)b;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int irgan_area_resize_u8(const void* src, int32_t N, int32_t Hin, int32_t Win, int32_t C, int64_t img_stride,
@@ -183,6 +308,35 @@ extern "C" int irgan_linear_area_resize_u8(const void* src, int32_t N, int32_t H
     linear_area_u8_kernel<<<g, TPB, 0, (hipStream_t)s>>>((const uint8_t*)src, Hin, Win, C, img_stride, yofs, ycoef,
                                                          Hout, xofs, xcoef, xlim, Wout, (const uint8_t*)flip,
                                                          (uint8_t*)out_u8, img_max);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_u8_native_to_unit(const void* src, int32_t N, int32_t H, int32_t W, int32_t C, int64_t img_stride,
+                                       const void* flip, int32_t max_rule, int32_t* img_max, float* out, void* out_u8,
+                                       irgan_stream_t s) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    if (!src || !out || (max_rule && !img_max) || C < 1 || C > 4 || img_stride < (long)H * W * C || N > 65535)
+        return IRGAN_EINVAL;
+    if (max_rule) {   // the whole image's max decides every pixel (ir:1142): its own pass first
+        const long len = (long)H * W * C;
+        const int bx = (int)std::min<long>(irgan_cdiv(len, TPB * 32), 128);
+        max_u8_kernel<<<dim3(bx, N), TPB, 0, (hipStream_t)s>>>((const uint8_t*)src, len, img_stride, img_max);
+        IRGAN_LAUNCH_CHECK();
+    }
+    const int U = irgan_cdiv(W, RUN) + 1;
+    const dim3 g(irgan_cdiv((long)H * U, TPB), N);
+#define IRGAN_NATIVE(CC)                                                                                          \
+    native_unit_kernel<CC><<<g, TPB, 0, (hipStream_t)s>>>((const uint8_t*)src, H, W, img_stride, U,               \
+                                                          (const uint8_t*)flip, img_max, max_rule, out,           \
+                                                          (uint8_t*)out_u8)
+    switch (C) {
+        case 1: IRGAN_NATIVE(1); break;
+        case 2: IRGAN_NATIVE(2); break;
+        case 3: IRGAN_NATIVE(3); break;
+        default: IRGAN_NATIVE(4); break;
+    }
+#undef IRGAN_NATIVE
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -17,6 +17,12 @@ horizontal flip -> x * 2 - 1.  At ~1,000 img/s per GPU that is the bottleneck
   ``irgan_area_resize_u8`` + one ``irgan_u8_to_unit`` launch per modality turn
   into the [-1, 1] device batch (csrc/data.hip).  ``train_kaist`` uses this path.
 
+``img_size`` is read in one place, ``target_hw``: an int S (the reference's S x S), a
+(height, width) pair, or None for each image's own size (the reference loaders'
+img_size=None, ir:817, 847).  A rectangular target follows cv::resize's own dispatch
+per call (copy / area tables per axis / the linear path when either axis upscales);
+at the source size the device path is one ``irgan_u8_native_to_unit`` launch.
+
 Decoding: OpenCV is not available in this image, so files are decoded with PIL
 and converted with cv2's rules (IMREAD_GRAYSCALE: 16-bit PNG -> high byte,
 colour -> BGR2GRAY fixed-point weights; IMREAD_COLOR + BGR2RGB).  INTER_AREA is
@@ -38,7 +44,7 @@ import torch
 from . import _lib
 from .ops import P, stream
 
-__all__ = ["EXTS", "area_table", "linear_area_table", "resize_area_u8", "resize_linear_area_u8", "imread_gray", "imread_rgb", "load_ir_image", "load_rgb_image",
+__all__ = ["EXTS", "target_hw", "parse_img_size", "area_table", "linear_area_table", "resize_area_u8", "resize_linear_area_u8", "imread_gray", "imread_rgb", "load_ir_image", "load_rgb_image",
            "collect_kaist_ir_files_from_sets", "scan_kaist_pairs", "KAISTPairDataset", "DeviceResizer",
            "collate_raw", "kaist_loader"]
 
@@ -161,28 +167,87 @@ def _slots(ptr, src, w):
     return out
 
 
-def resize_area_u8(img: np.ndarray, size: int) -> np.ndarray:
-    """cv2.resize(img, (size, size), interpolation=INTER_AREA) for uint8 HxW or
-    HxWxC input, host side.  Both axes downscaling (OpenCV's area path): float32 in
+def _whole(v):
+    if isinstance(v, (bool, np.bool_)):
+        return None
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    if isinstance(v, (float, np.floating)) and float(v).is_integer():
+        return int(v)
+    return None
+
+
+def target_hw(img_size, src_hw=None):
+    """The one reading of ``img_size`` (Config, the loaders, the datasets, DeviceResizer,
+    run_test) -> the (h, w) an image of source size ``src_hw`` is brought to:
+
+    * an int S: (S, S), the reference's square resize (ir:818, 1139);
+    * a pair (H, W), tuple or list: HEIGHT FIRST, the order of a (B, C, H, W) tensor's
+      last two axes -- the opposite of cv2.resize's dsize, which is (width, height);
+    * None: ``src_hw`` itself, each image keeps its size (the loaders' img_size=None,
+      ir:817, 847); with no source to be native to (src_hw None) that is an error.
+
+    Integral floats count as ints; anything else raises ValueError."""
+    if img_size is None:
+        if src_hw is None:
+            raise ValueError("img_size=None keeps the source size, and there is no source here")
+        return int(src_hw[0]), int(src_hw[1])
+    s = _whole(img_size)
+    if s is not None:
+        hw = (s, s)
+    elif isinstance(img_size, (tuple, list)) and len(img_size) == 2:
+        hw = (_whole(img_size[0]), _whole(img_size[1]))
+    else:
+        hw = (None, None)
+    if hw[0] is None or hw[1] is None or hw[0] < 1 or hw[1] < 1:
+        raise ValueError(f"img_size must be a positive int, a (height, width) pair of them or None, got {img_size!r}")
+    return hw
+
+
+def parse_img_size(text: str):
+    """The command line's ``--img-size N | HxW | native`` as an ``img_size`` value."""
+    t = text.strip().lower()
+    if t == "native":
+        return None
+    try:
+        parts = [int(p) for p in t.split("x")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2):
+        raise ValueError(f"--img-size takes N, HxW (height first) or 'native', got {text!r}")
+    size = parts[0] if len(parts) == 1 else tuple(parts)
+    target_hw(size)
+    return size
+
+
+def resize_area_u8(img: np.ndarray, size) -> np.ndarray:
+    """cv2.resize(img, (w, h), interpolation=INTER_AREA) for uint8 HxW or HxWxC input,
+    host side, with (h, w) = target_hw(size, img.shape[:2]) -- note the order: ``size``
+    is an int or (HEIGHT, WIDTH), cv2's dsize is (width, height).  cv::resize's dispatch:
+    a target equal to the source size returns a copy (dsize == ssize); both axes with
+    scale >= 1 take OpenCV's area path, each axis with its own table: float32 in
     OpenCV's operation order -- per destination row, each source row of its cell
     reduced horizontally (buf = 0 + a0*S0 + a1*S1 ...), then sum = b0*buf0 + b1*buf1
-    ..., rounded half to even and clamped to uint8.  Otherwise (an img_size above the
-    source size): resize_linear_area_u8."""
+    ..., rounded half to even and clamped to uint8; either axis upscaling sends the whole
+    image through resize_linear_area_u8."""
     a = np.asarray(img)
-    if a.shape[0] < size or a.shape[1] < size:
-        return resize_linear_area_u8(a, size, size)
+    h, w = target_hw(size, a.shape[:2])
+    if (h, w) == tuple(a.shape[:2]):
+        return a.copy()
+    if a.shape[0] < h or a.shape[1] < w:
+        return resize_linear_area_u8(a, w, h)
     squeeze = a.ndim == 2
     if squeeze:
         a = a[:, :, None]
     H, W, C = a.shape
-    yt = _slots(*area_table(H, size))
-    xt = _slots(*area_table(W, size))
+    yt = _slots(*area_table(H, h))
+    xt = _slots(*area_table(W, w))
     S = a.astype(np.float32)
-    # horizontal pass for every source row: (H, size, C)
-    buf = np.zeros((H, size, C), np.float32)
+    # horizontal pass for every source row: (H, w, C)
+    buf = np.zeros((H, w, C), np.float32)
     for d, s, wt in xt:
         buf[:, d, :] = buf[:, d, :] + S[:, s, :] * wt[None, :, None]
-    out = np.zeros((size, size, C), np.float32)
+    out = np.zeros((h, w, C), np.float32)
     for t, (d, s, wt) in enumerate(yt):
         term = buf[s, :, :] * wt[:, None, None]
         out[d] = term if t == 0 else out[d] + term
@@ -232,19 +297,15 @@ def _unit_ir(img_u8: np.ndarray) -> np.ndarray:
 
 
 def load_ir_image(path, img_size=None):
-    """ir:803-830: HxW float32 in [0, 1], optionally INTER_AREA-resized."""
-    img = imread_gray(path)
-    if img_size is not None:
-        img = resize_area_u8(img, img_size)
-    return _unit_ir(img)
+    """ir:803-830: HxW float32 in [0, 1], INTER_AREA-resized to ``img_size`` (target_hw's
+    forms; None, the default, keeps the source size)."""
+    return _unit_ir(resize_area_u8(imread_gray(path), img_size))
 
 
 def load_rgb_image(path, img_size=None):
-    """ir:833-852: HxWx3 float32 RGB in [0, 1], optionally INTER_AREA-resized."""
-    img = imread_rgb(path)
-    if img_size is not None:
-        img = resize_area_u8(img, img_size)
-    return np.clip(img.astype(np.float32) / 255.0, 0.0, 1.0)
+    """ir:833-852: HxWx3 float32 RGB in [0, 1], INTER_AREA-resized to ``img_size``
+    (target_hw's forms; None, the default, keeps the source size)."""
+    return np.clip(resize_area_u8(imread_rgb(path), img_size).astype(np.float32) / 255.0, 0.0, 1.0)
 
 
 def _list_imgs(folder):
@@ -301,10 +362,12 @@ def scan_kaist_pairs(roots):
 
 class KAISTPairDataset(torch.utils.data.Dataset):
     """ir:1045-1177 with the reference's signature and item contract; see the
-    module docstring for the device path (``raw`` + ``kaist_loader``)."""
+    module docstring for the device path (``raw`` + ``kaist_loader``).  ``img_size``:
+    target_hw's forms -- an int, (height, width), or None for each pair's own size."""
 
     def __init__(self, root, img_size=256, augment=True, indices=None, verbose=True):
         super().__init__()
+        target_hw(img_size, (1, 1))   # reject a malformed size here, not in a worker
         self.img_size, self.augment = img_size, augment
         all_ir, all_rgb = scan_kaist_pairs(root)
         if indices is not None:
@@ -367,62 +430,82 @@ def collate_raw(items):
 
 
 class DeviceResizer:
-    """uint8 decoded batch -> {'ir': (B,1,S,S), 'rgb': (B,3,S,S)} float32 [-1, 1] on
-    the device: per modality one area-resize+flip launch and one normalisation
-    launch (the IR max rule of ir:1142 included).  Tables cached per size."""
+    """uint8 decoded batch -> {'ir': (B,1,h,w), 'rgb': (B,3,h,w)} float32 [-1, 1] on
+    the device, (h, w) = target_hw(img_size, source size): per modality one
+    area-resize+flip launch and one normalisation launch (the IR max rule of ir:1142
+    included), or, where the target is the source size, the single native pass
+    (irgan_u8_native_to_unit).  Tables cached per (source n, target n)."""
 
     def __init__(self, img_size, device):
-        self.size, self.device = img_size, torch.device(device)
+        target_hw(img_size, (1, 1))
+        self.img_size, self.device = img_size, torch.device(device)
         self._tabs = {}
 
-    def _tab(self, n):
-        t = self._tabs.get(n)
+    def _tab(self, n, d):
+        t = self._tabs.get((n, d))
         if t is None:
-            t = self._tabs[n] = tuple(torch.from_numpy(a).to(self.device) for a in area_table(n, self.size))
+            t = self._tabs[(n, d)] = tuple(torch.from_numpy(a).to(self.device) for a in area_table(n, d))
         return t
 
-    def _ltab(self, n, columns):
-        key = ("lin", n, columns)
+    def _ltab(self, n, d, columns):
+        key = ("lin", n, d, columns)
         t = self._tabs.get(key)
         if t is None:
-            ofs, coef, lim = linear_area_table(n, self.size, columns)
+            ofs, coef, lim = linear_area_table(n, d, columns)
             t = self._tabs[key] = (torch.from_numpy(ofs).to(self.device), torch.from_numpy(coef).to(self.device), lim)
         return t
 
-    def resize_u8(self, u8, C, flip=None, img_max=None):
-        """(B,H,W[,C]) uint8 device batch -> (B,C,S,S) uint8 (cv2.resize INTER_AREA,
-        optional per-image horizontal flip)."""
+    def resize_u8(self, u8, C, flip=None, img_max=None, hw=None):
+        """(B,H,W[,C]) uint8 device batch -> (B,C,h,w) uint8 (cv2.resize INTER_AREA,
+        optional per-image horizontal flip).  ``hw`` overrides the resizer's own target
+        (run_test: the ground truth goes to its prediction's size)."""
         if u8.dtype != torch.uint8 or not u8.is_cuda:
             raise ValueError("resize_u8 takes a uint8 device tensor")
         u8 = u8.contiguous()
         B, H, W = u8.shape[:3]
-        S = self.size
-        out8 = torch.empty(B, C, S, S, dtype=torch.uint8, device=self.device)
-        if H < S or W < S:   # an upscaling axis: OpenCV's linear path with area coefficients
-            yo, yc, _ = self._ltab(H, False)
-            xo, xc, xlim = self._ltab(W, True)
-            _lib.call("irgan_linear_area_resize_u8", P(u8), B, H, W, C, ctypes.c_int64(H * W * C), P(yo), P(yc), S,
-                      P(xo), P(xc), xlim, S, P(flip) if flip is not None else None, P(out8),
+        h, w = hw if hw is not None else target_hw(self.img_size, (H, W))
+        out8 = torch.empty(B, C, h, w, dtype=torch.uint8, device=self.device)
+        if H < h or W < w:   # an upscaling axis: OpenCV's linear path with area coefficients
+            yo, yc, _ = self._ltab(H, h, False)
+            xo, xc, xlim = self._ltab(W, w, True)
+            _lib.call("irgan_linear_area_resize_u8", P(u8), B, H, W, C, ctypes.c_int64(H * W * C), P(yo), P(yc), h,
+                      P(xo), P(xc), xlim, w, P(flip) if flip is not None else None, P(out8),
                       P(img_max) if img_max is not None else None, stream())
             return out8
-        yp, ys, yw = self._tab(H)
-        xp, xs, xw = self._tab(W)
-        _lib.call("irgan_area_resize_u8", P(u8), B, H, W, C, ctypes.c_int64(H * W * C), P(yp), P(ys), P(yw), S,
-                  P(xp), P(xs), P(xw), S, P(flip) if flip is not None else None, P(out8),
+        yp, ys, yw = self._tab(H, h)   # (an axis that keeps its size: the identity table, unit weights)
+        xp, xs, xw = self._tab(W, w)
+        _lib.call("irgan_area_resize_u8", P(u8), B, H, W, C, ctypes.c_int64(H * W * C), P(yp), P(ys), P(yw), h,
+                  P(xp), P(xs), P(xw), w, P(flip) if flip is not None else None, P(out8),
                   P(img_max) if img_max is not None else None, stream())
         return out8
 
     def _one(self, u8, C, flip, max_rule, keep_u8=False):
-        """(B,C,S,S) float32 [-1, 1]; keep_u8: also the resized uint8 batch (what the
+        """(B,C,h,w) float32 [-1, 1]; keep_u8: also the resized uint8 batch (what the
         reference's loaders hold before their float conversion)."""
-        B, S = u8.shape[0], self.size
+        B, H, W = u8.shape[:3]
+        h, w = target_hw(self.img_size, (H, W))
         mx = torch.zeros(B, dtype=torch.int32, device=self.device)
+        out = torch.empty(B, C, h, w, dtype=torch.float32, device=self.device)
+        if (h, w) == (H, W):   # nothing to resize: uint8 NHWC -> float NCHW in one pass
+            if u8.dtype != torch.uint8 or not u8.is_cuda:
+                raise ValueError("the device path takes a uint8 device tensor")
+            u8 = u8.contiguous()
+            out8 = torch.empty(B, C, h, w, dtype=torch.uint8, device=self.device) if keep_u8 else None
+            _lib.call("irgan_u8_native_to_unit", P(u8), B, H, W, C, ctypes.c_int64(H * W * C),
+                      P(flip) if flip is not None else None, int(max_rule), P(mx), P(out),
+                      P(out8) if keep_u8 else None, stream())
+            return (out, out8) if keep_u8 else out
         out8 = self.resize_u8(u8, C, flip, mx)
-        out = torch.empty(B, C, S, S, dtype=torch.float32, device=self.device)
-        _lib.call("irgan_u8_to_unit", P(out8), B, ctypes.c_int64(C * S * S), P(mx), int(max_rule), P(out), stream())
+        _lib.call("irgan_u8_to_unit", P(out8), B, ctypes.c_int64(C * h * w), P(mx), int(max_rule), P(out), stream())
         return (out, out8) if keep_u8 else out
 
     def __call__(self, batch):
+        hw_ir = target_hw(self.img_size, batch["ir_u8"].shape[1:3])
+        hw_rgb = target_hw(self.img_size, batch["rgb_u8"].shape[1:3])
+        if hw_ir != hw_rgb:
+            raise RuntimeError(f"img_size=None keeps each image's own size, but this batch's IR frames are "
+                               f"{hw_ir[0]}x{hw_ir[1]} and its RGB frames {hw_rgb[0]}x{hw_rgb[1]}: such a pair "
+                               "cannot be stacked for the loss -- give an img_size")
         ir8 = batch["ir_u8"].to(self.device, non_blocking=True).contiguous()
         rgb8 = batch["rgb_u8"].to(self.device, non_blocking=True).contiguous()
         flip = batch["flip"].to(self.device, non_blocking=True)
@@ -444,7 +527,8 @@ class _DeviceLoader:
 def kaist_loader(dataset: KAISTPairDataset, batch_size, device, shuffle=False, drop_last=False, num_workers=0,
                  sampler=None):
     """DataLoader over ``dataset.raw`` (workers decode only) whose batches are
-    resized / flipped / normalised on ``device`` (DeviceResizer)."""
+    resized / flipped / normalised on ``device`` (DeviceResizer) to ``dataset.img_size``
+    (target_hw's forms; None: the batch's own size, one size per batch by collate_raw)."""
     base = dataset.dataset if isinstance(dataset, torch.utils.data.Subset) else dataset
     dl = torch.utils.data.DataLoader(_RawView(dataset), batch_size=batch_size, shuffle=shuffle and sampler is None,
                                      sampler=sampler, num_workers=num_workers, collate_fn=collate_raw,

@@ -161,7 +161,10 @@ def _batches(entries, size, bs):
 
 @torch.no_grad()
 def run_test(cfg, model=None, log=print):
-    """ir:1333-1514 on the device, ``cfg.test_batch`` frames per generator call."""
+    """ir:1333-1514 on the device, ``cfg.test_batch`` frames per generator call.
+    ``cfg.img_size`` in data.target_hw's forms: S, (height, width), or None for every
+    frame at its own size (``_batches`` cuts a batch where the source size changes);
+    predictions, resized ground truth, metrics and collage panels are then h x w."""
     from .ir_colorization import IRColorizationModel
     device = torch.device(cfg.device)
     log(f"[TEST] Device: {device}")
@@ -205,7 +208,8 @@ def run_test(cfg, model=None, log=print):
         gt_u8 = {}
         if have:
             g8 = torch.from_numpy(np.stack([D.imread_rgb(gts[i]) for i in have])).to(device)
-            g_res = resizer.resize_u8(g8, 3).permute(0, 2, 3, 1).contiguous()   # (h, S, S, 3)
+            # to the predictions' (h, w): under img_size=None that is the IR frames' own size
+            g_res = resizer.resize_u8(g8, 3, hw=tuple(ir_t.shape[2:])).permute(0, 2, 3, 1).contiguous()
             for i, m in zip(have, image_metrics_u8(pred8[have], g_res)):
                 mets[i] = m
             for i, g in zip(have, g_res.cpu().numpy()):

@@ -52,7 +52,7 @@ class Config:
     def __init__(self):
         self.mode = "test"
         self.device = "cuda" if torch.cuda.is_available() else "cpu"
-        self.img_size = 256
+        self.img_size = 256              # S (S x S), (height, width), or None = native size (data.target_hw)
         self.input_nc = 1
         self.output_nc = 3
         self.ngf = 64
@@ -828,12 +828,15 @@ def val_shard(val_ds, rank, world):
 
 class SyntheticPairDataset(torch.utils.data.Dataset):
     """KAISTPairDataset item contract (ir:1171-1177): {'ir': 1xHxW, 'rgb': 3xHxW}
-    in [-1,1]; seeded uniform data (the KAIST dataset is not shipped)."""
+    in [-1,1]; seeded uniform data (the KAIST dataset is not shipped).  ``img_size``: an
+    int or (height, width) (data.target_hw); None raises, there is no source size to keep."""
 
     def __init__(self, n, img_size=256, seed=7, input_nc=1, output_nc=3):
+        from .data import target_hw
+        h, w = target_hw(img_size)
         g = torch.Generator().manual_seed(seed)
-        self.ir = torch.rand(n, input_nc, img_size, img_size, generator=g) * 2 - 1
-        self.rgb = torch.rand(n, output_nc, img_size, img_size, generator=g) * 2 - 1
+        self.ir = torch.rand(n, input_nc, h, w, generator=g) * 2 - 1
+        self.rgb = torch.rand(n, output_nc, h, w, generator=g) * 2 - 1
 
     def __len__(self):
         return self.ir.shape[0]
@@ -845,7 +848,8 @@ class SyntheticPairDataset(torch.utils.data.Dataset):
 def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
     """ir:1549-1723 with the fused HIP step.  ``dataset=None`` trains on the KAIST
     pairs under ``cfg.train_roots`` (data.KAISTPairDataset: decode on the host,
-    INTER_AREA resize + paired flip + normalisation on the device); any dataset
+    INTER_AREA resize to ``cfg.img_size`` -- S, (height, width) or None for the frames'
+    own size -- + paired flip + normalisation on the device); any dataset
     yielding {'ir','rgb'} (e.g. SyntheticPairDataset) may be passed instead.
     ``trainer_hook(trainer)`` (optional) runs once after the networks are built
     (e.g. to load D / VGG weights from files)."""
