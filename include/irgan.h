@@ -548,6 +548,19 @@ IRGAN_API int irgan_adam(float* p, const float* g, float* m, float* v, int64_t n
 IRGAN_API int irgan_adam_prep(int32_t* count, double lr, double beta1, double beta2, float* prm, irgan_stream_t s);
 IRGAN_API int irgan_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* prm, float beta1,
                    float beta2, float eps, irgan_stream_t s);
+/* The same three with an exponential moving average of the parameters updated in the same
+ * pass: per element, after the Adam update, ema += ema_weight * (p_new - ema).  p, m, v are
+ * bit-identical to the plain entries.  ema_weight = 1 - min(decay, (1 + t) / (10 + t)) for
+ * the 1-based step t (fp64 -> fp32); irgan_adam_ema_prep (decay in [0, 1), else
+ * IRGAN_EINVAL) writes it to prm[2] beside prm[0], prm[1], so its prm holds THREE floats.
+ * Any 4-byte-aligned pointers and n >= 1: 16-byte accesses when the five pointers share one
+ * offset from a 16-byte boundary (scalar head / tail), one element per lane otherwise. */
+IRGAN_API int irgan_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float step_size,
+                   float beta1, float beta2, float bc2_sqrt, float eps, float ema_weight, irgan_stream_t s);
+IRGAN_API int irgan_adam_ema_prep(int32_t* count, double lr, double beta1, double beta2, double ema_decay,
+                   float* prm, irgan_stream_t s);
+IRGAN_API int irgan_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                   const float* prm, float beta1, float beta2, float eps, irgan_stream_t s);
 
 /* ---- inference / evaluation ---- */
 /* out[p][c] = uint8(clip((x + 1) / 2, 0, 1) * 255) for every pixel p and

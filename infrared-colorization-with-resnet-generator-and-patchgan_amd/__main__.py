@@ -1,8 +1,9 @@
 """``python -m infrared-colorization-with-resnet-generator-and-patchgan_amd [train|test]
-[--img-size N | HxW | native]`` -- the reference's script entry point (ir:1730-1756) with
+[--img-size N | HxW | native] [--ema-decay D]`` -- the reference's script entry point (ir:1730-1756) with
 cfg.mode taken from the command line (default: Config's "test").  ``--img-size`` sets
 cfg.img_size: N for N x N, HxW (height first, e.g. 512x640) or ``native`` for every frame
-at its own size; without the flag Config's value stands."""
+at its own size; ``--ema-decay`` sets cfg.ema_decay (e.g. 0.999: train with a moving average
+of the generator weights).  Without a flag Config's value stands."""
 import argparse
 import sys
 
@@ -14,12 +15,15 @@ def config_from_argv(argv):
     ap = argparse.ArgumentParser(prog="python -m infrared-colorization-with-resnet-generator-and-patchgan_amd")
     ap.add_argument("mode", nargs="?", help="train or test (default: Config.mode)")
     ap.add_argument("--img-size", type=parse_img_size, default=argparse.SUPPRESS, metavar="N|HxW|native")
+    ap.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, metavar="D")
     a = ap.parse_args(argv)
     cfg = Config()
     if a.mode is not None:
         cfg.mode = a.mode
     if hasattr(a, "img_size"):
         cfg.img_size = a.img_size
+    if hasattr(a, "ema_decay"):
+        cfg.ema_decay = a.ema_decay
     return cfg
 
 

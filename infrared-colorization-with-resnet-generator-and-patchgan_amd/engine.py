@@ -157,9 +157,10 @@ class ParamStore:
         self.grad = torch.zeros(off, device=device) if with_grad else None
         self.m = torch.zeros(off, device=device) if with_adam else None
         self.v = torch.zeros(off, device=device) if with_adam else None
+        self.ema = None         # enable_ema(): the parameters' moving average, updated by Adam's pass
         self.step_count = 0
         self.dev_adam = False   # GANStep: step count on the device (irgan_adam_prep)
-        self._count = self._prm = None
+        self._count = self._prm = self._prm_ema = None
         self._count_host = 0
 
     def krsc(self, k, buf=None):
@@ -243,10 +244,31 @@ class ParamStore:
     def adam_step(self, lr, b1=0.5, b2=0.999, eps=1e-8):
         self.adam_begin(lr, b1, b2, eps)(0, self.numel)
 
-    def adam_begin(self, lr, b1=0.5, b2=0.999, eps=1e-8):
+    @torch.no_grad()
+    def enable_ema(self):
+        """Allocate ``ema`` as a copy of the parameters as they are now (once; a second call
+        keeps the average)."""
+        if self.ema is None:
+            self.ema = self.flat.clone()
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the CONTENTS of ``flat`` and ``ema``: the packs and the modules' parameters
+        point into ``flat``, so the tensors stay where they are.  The caller repacks."""
+        if self.ema is None:
+            raise RuntimeError("swap_ema: no EMA buffer (enable_ema() first)")
+        tmp = self.flat.clone()
+        self.flat.copy_(self.ema)
+        self.ema.copy_(tmp)
+
+    def adam_begin(self, lr, b1=0.5, b2=0.999, eps=1e-8, ema_decay=0.0):
         """Count one optimizer step and return apply(start, end), the Adam update of
         the flat slice [start, end): a step may be applied bucket by bucket as each
-        bucket's gradient all-reduce completes (BucketedAllreduce.finish)."""
+        bucket's gradient all-reduce completes (BucketedAllreduce.finish).  With ``ema_decay``
+        and an ``ema`` buffer the same launch also moves ema[start:end] towards the new
+        parameters (ops.ema_weight); otherwise ``ema`` is not touched."""
+        if ema_decay and self.ema is not None:
+            return self._adam_ema_begin(lr, b1, b2, eps, ema_decay)
         self.step_count += 1
         t = self.step_count
         if self.dev_adam:
@@ -267,6 +289,34 @@ class ParamStore:
 
         def apply(a, b):
             ops.adam(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], t, lr, b1, b2, eps)
+        return apply
+
+    def _adam_ema_begin(self, lr, b1, b2, eps, decay):
+        """adam_begin's two paths on the EMA kernels.  The device count is the one the plain
+        path uses; the parameter block is this path's own three floats (the plain entries'
+        prm stays two)."""
+        self.step_count += 1
+        t = self.step_count
+        if self.dev_adam:
+            if self._count is None:
+                self._count = torch.zeros(1, dtype=torch.int32, device=self.device)
+                self._prm = torch.zeros(2, dtype=torch.float32, device=self.device)
+                self._count_host = 0
+            if self._prm_ema is None:
+                self._prm_ema = torch.zeros(3, dtype=torch.float32, device=self.device)
+            if self._count_host != t - 1:
+                self._count.fill_(t - 1)
+            ops.adam_ema_prep(self._count, lr, b1, b2, decay, self._prm_ema)
+            self._count_host = t
+
+            def apply_dev(a, b):
+                ops.adam_ema_dev(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], self.ema[a:b],
+                                 self._prm_ema, b1, b2, eps)
+            return apply_dev
+
+        def apply(a, b):
+            ops.adam_ema(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], self.ema[a:b], t, lr, b1, b2,
+                         eps, decay)
         return apply
 
 
@@ -1540,6 +1590,9 @@ class GANStep:
         if cfg.norm == "batch" and getattr(cfg, "sync_bn", False) and self.g_reduce.active:
             self.gen.bn_sync = self.dis.bn_sync = BNSync(process_group)
         self.lr_scale = 1.0
+        # Config.ema_decay > 0: G's Adam launches also update G.ema (ParamStore.adam_begin); the
+        # owner allocates it (G.enable_ema()), and 0 is the plain path with no buffer
+        self.ema_decay = float(getattr(cfg, "ema_decay", 0.0) or 0.0)
         # the D step (D forward/backward on [real; fake] and its all-reduce) runs on a
         # side stream, concurrently with the G-step terms that do not read D (L1,
         # VGG, TV, SSIM); IRGAN_NO_D_OVERLAP=1 keeps everything on one stream
@@ -1677,7 +1730,8 @@ class GANStep:
             _mark(ph, "join", main)
         ops.axpby(dd.sl(cin, cout), 1.0, Feat(dfake), 1.0)
         self.gen.backward(dfake, ready=self.g_reduce.ready)
-        self.g_reduce.finish(self.G.adam_begin(cfg.lr_G * self.lr_scale, cfg.beta1, cfg.beta2))
+        self.g_reduce.finish(self.G.adam_begin(cfg.lr_G * self.lr_scale, cfg.beta1, cfg.beta2,
+                                               ema_decay=self.ema_decay))
         self.gen.pack()
         if ph is not None:
             _mark(ph, "end", main)

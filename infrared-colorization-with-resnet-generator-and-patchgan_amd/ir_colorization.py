@@ -21,6 +21,7 @@ GPU kernels (autograd.Function wrappers), and there is no CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import math
 import os
@@ -103,6 +104,8 @@ class Config:
         self.deterministic = False       # ops.set_deterministic: bitwise-reproducible weight gradients
         self.sync_bn = False             # norm='batch' under data parallelism: BatchNorm statistics over all
                                          # ranks (nn.SyncBatchNorm semantics) in the fused step; off -> refused
+        self.ema_decay = 0.0             # in (0, 1): keep an exponential moving average of G's weights (updated
+                                         # in G's Adam pass); train_kaist validates and saves it as netG_ema_*.pth
 
 
 # =============================================================================
@@ -673,6 +676,14 @@ def _refuse_multi_rank_batch_norm(cfg, process_group=None):
                                   "norm='instance' / 'none'")
 
 
+def _check_ema_decay(cfg):
+    """Config.ema_decay as a float; ValueError outside [0, 1) (0 = off)."""
+    d = float(getattr(cfg, "ema_decay", 0.0) or 0.0)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1) (0 turns the weight average off), got {d!r}")
+    return d
+
+
 class GANTrainer:
     """Owns G (through the model), D, VGG and both Adams; ``step(ir, rgb)`` runs
     the fused HIP train step and returns the device loss vector (no host sync)."""
@@ -683,6 +694,7 @@ class GANTrainer:
         (engine.BucketedAllreduce; needs an initialised process group)."""
         self.cfg = cfg
         _refuse_multi_rank_batch_norm(cfg, process_group)   # before any GPU work
+        self.ema_decay = _check_ema_decay(cfg)              # likewise
         dev = torch.device(cfg.device)
         dt = getattr(cfg, "compute_dtype", "bf16")
         if getattr(cfg, "deterministic", False):
@@ -702,10 +714,50 @@ class GANTrainer:
                             vgg=self.vgg.engine, force_reduce=force_reduce)
         self.lr_lambda = get_lr_lambda(cfg)
         self.epoch_index = 0
+        self._in_ema = False
+        if self.ema_decay > 0:
+            self.netG.store.enable_ema()   # a copy of G as built (init_G_weights already loaded)
 
     def step(self, ir, rgb):
         _require_cuda(ir, "GANTrainer.step")
+        if self._in_ema:
+            raise RuntimeError("GANTrainer.step inside ema_weights(): the generator holds the averaged weights")
         return self.core.step(ir, rgb)
+
+    # ---- Config.ema_decay: the moving average of G's parameters (ParamStore.ema, updated by G's
+    # Adam launches).  Only the parameters are averaged: under norm='batch' the EMA generator
+    # runs with the live running statistics, under compute_dtype='fp8' with the live
+    # delayed-scaling state (its e4m3 weight scales are recomputed by the repack, as for any weights).
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the generator (``model(ir)``, ``netG.state_dict()``) holds the EMA
+        weights and ``store.ema`` the live ones; the exit swaps them back, on exceptions too."""
+        if self.ema_decay <= 0:
+            raise RuntimeError("ema_weights(): EMA is off (Config.ema_decay = 0)")
+        if self._in_ema:
+            raise RuntimeError("ema_weights() is already entered")
+        self.netG.store.swap_ema()
+        self.netG._dirty = True
+        self._in_ema = True
+        try:
+            yield self.model
+        finally:
+            self.netG.store.swap_ema()
+            self.netG.repack()   # not just dirty: the fused step reads the packs as they are
+            self._in_ema = False
+
+    def ema_state_dict(self):
+        """A generator state_dict in the reference's layout (contiguous OIHW fp32 on the CPU): the
+        EMA parameters and the live buffers.  IRColorizationModel.load_weights and the
+        reference's netG.load_state_dict take it."""
+        if self.ema_decay <= 0:
+            raise RuntimeError("ema_state_dict(): EMA is off (Config.ema_decay = 0)")
+        S = self.netG.store
+        ema = S.ema if not self._in_ema else S.flat
+        sd = _cpu_state(self.netG)
+        for k in S.shapes:
+            sd[k] = S.oihw(k, ema).detach().contiguous().cpu()
+        return sd
 
     def losses(self, L):
         return GANStep.loss_dict(L, self.cfg)
@@ -727,6 +779,8 @@ class GANTrainer:
     # generator's delayed-scaling state (netG.fp8_state_dict()), without which the resumed run
     # would recalibrate every slot on its first step; the other dtypes' dicts have no such key.
     def state_dict(self):
+        if self._in_ema:
+            raise RuntimeError("GANTrainer.state_dict inside ema_weights()")
         c, s = self.cfg, self.core
         sd = {"netG": {k: v.detach().cpu().clone() for k, v in self.netG.store.state().items()},
               "netD": {k: v.detach().cpu().clone() for k, v in self.netD.store.state().items()},
@@ -735,17 +789,32 @@ class GANTrainer:
               "epoch_index": self.epoch_index, "lr_scale": s.lr_scale}
         if self.netG.engine.fp8:
             sd["fp8"] = self.netG.fp8_state_dict()
+        if self.ema_decay > 0:
+            S = self.netG.store
+            sd["ema"] = {k: v.detach().cpu().clone() for k, v in S.state(buf=S.ema).items()}
         return sd
 
     def load_state_dict(self, sd):
         """An fp8 trainer restores the "fp8" entry, or, given a file without one, starts from
-        unseen scale slots; a trainer of another dtype ignores the entry."""
+        unseen scale slots; a trainer of another dtype ignores the entry.  With EMA on, "ema" is
+        restored, or, given a file without it, the average restarts from the loaded parameters;
+        with EMA off the entry is ignored."""
+        if self._in_ema:
+            raise RuntimeError("GANTrainer.load_state_dict inside ema_weights()")
         self.netG.store.load(sd["netG"], strict=True)
         self.netD.store.load(sd["netD"], strict=True)
         self.netG.store.load_adam_state_dict(sd["optimizer_G"])
         self.netD.store.load_adam_state_dict(sd["optimizer_D"])
         self.epoch_index = int(sd["epoch_index"])
         self.core.lr_scale = float(sd["lr_scale"])
+        if self.ema_decay > 0:
+            S = self.netG.store
+            with torch.no_grad():
+                if "ema" in sd:
+                    for k in S.shapes:
+                        S.oihw(k, S.ema).copy_(sd["ema"][k].to(S.device, torch.float32))
+                else:
+                    S.ema.copy_(S.flat)
         for net in (self.netG, self.netD):
             net.repack()
         if self.netG.engine.fp8:
@@ -895,6 +964,9 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
         os.makedirs(cfg.save_dir, exist_ok=True)
     best_val = float("inf")
     best_path = os.path.join(cfg.save_dir, "netG_best.pth")
+    ema_on = trainer.ema_decay > 0
+    best_val_ema = float("inf")
+    best_ema_path = os.path.join(cfg.save_dir, "netG_ema_best.pth")
     history = []
     for epoch in range(1, cfg.epochs + 1):
         if sampler is not None:
@@ -919,7 +991,24 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
         log(f"Epoch [{epoch}/{cfg.epochs}] DONE | avg D: {avg['loss_D']:.4f} | avg G: {avg['loss_G']:.4f} | "
             f"val L1: {val_l1:.4f}")
         history.append(dict(epoch=epoch, val_l1=val_l1, **avg))
-        if rank == 0 and ((epoch % cfg.save_every == 0) or (epoch == cfg.epochs)):
+        periodic = (epoch % cfg.save_every == 0) or (epoch == cfg.epochs)
+        if ema_on:
+            # the averaged generator: validated and saved like the live one, under its own
+            # names and its own best-so-far (every rank enters: validate_kaist all-reduces)
+            with trainer.ema_weights():
+                val_l1_ema = validate_kaist(model, val_loader, device)
+                log(f"Epoch [{epoch}/{cfg.epochs}] EMA (decay {trainer.ema_decay:g}) | val L1: {val_l1_ema:.4f}")
+                history[-1]["val_l1_ema"] = val_l1_ema
+                if rank == 0 and periodic:
+                    path = os.path.join(cfg.save_dir, f"netG_ema_epoch_{epoch:03d}.pth")
+                    _save_generator(model.netG, path)
+                    log(f"Saved EMA generator checkpoint to {path}")
+                if val_l1_ema < best_val_ema:
+                    best_val_ema = val_l1_ema
+                    if rank == 0:
+                        _save_generator(model.netG, best_ema_path)
+                    log(f"New best EMA model saved to {best_ema_path} (val L1={best_val_ema:.4f})")
+        if rank == 0 and periodic:
             path = os.path.join(cfg.save_dir, f"netG_epoch_{epoch:03d}.pth")
             _save_generator(model.netG, path)
             log(f"Saved generator checkpoint to {path}")
@@ -931,6 +1020,8 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
         trainer.scheduler_step()
         log(f"Current LR (G): {trainer.current_lr_G:.6e}")
     log(f"Training finished. Best val L1: {best_val:.4f}, best model: {best_path}")
+    if ema_on:
+        log(f"Best EMA val L1: {best_val_ema:.4f}, best EMA model: {best_ema_path}")
     return history
 
 

@@ -1124,6 +1124,46 @@ def adam_dev(p, g, m, v, prm: torch.Tensor, b1: float, b2: float, eps: float):
               ctypes.c_float(eps), stream())
 
 
+def ema_weight(decay: float, t: int) -> float:
+    """The weight of the new parameters in the EMA update after optimizer step ``t`` (1-based):
+    ``1 - min(decay, (1 + t) / (10 + t))``, so ``e += w * (p - e)``.  The warm-up term lets a
+    short run's average follow the weights instead of the initialisation.  fp64; the kernels
+    take it rounded to fp32 (irgan_adam_ema_prep evaluates the same formula on the device)."""
+    return 1.0 - min(float(decay), (1.0 + t) / (10.0 + t))
+
+
+def _same_numel(what, p, *others):
+    if any(t.numel() != p.numel() for t in others):
+        raise ValueError(f"{what}: p, g, m, v and ema must have one element count")
+
+
+def adam_ema(p, g, m, v, ema, step: int, lr: float, b1: float, b2: float, eps: float, decay: float):
+    """ops.adam and, in the same pass, ema += ema_weight(decay, step) * (p_new - ema)
+    (irgan_adam_ema); p, m, v come out as ops.adam leaves them, bit for bit."""
+    _same_numel("ops.adam_ema", p, g, m, v, ema)
+    bc1 = 1 - b1 ** step
+    bc2 = 1 - b2 ** step
+    _lib.call("irgan_adam_ema", P(p), P(g), P(m), P(v), P(ema), p.numel(), ctypes.c_float(lr / bc1),
+              ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(math.sqrt(bc2)), ctypes.c_float(eps),
+              ctypes.c_float(ema_weight(decay, step)), stream())
+
+
+def adam_ema_prep(count: torch.Tensor, lr: float, b1: float, b2: float, decay: float, prm: torch.Tensor):
+    """ops.adam_prep with prm (fp32[3]) = {step_size, bc2_sqrt, ema_weight(decay, t)}
+    (irgan_adam_ema_prep)."""
+    if prm.numel() < 3:
+        raise ValueError("ops.adam_ema_prep: prm holds three floats")
+    _lib.call("irgan_adam_ema_prep", P(count), ctypes.c_double(lr), ctypes.c_double(b1), ctypes.c_double(b2),
+              ctypes.c_double(decay), P(prm), stream())
+
+
+def adam_ema_dev(p, g, m, v, ema, prm: torch.Tensor, b1: float, b2: float, eps: float):
+    """ops.adam_ema with step_size / bc2_sqrt / the EMA weight read from prm (irgan_adam_ema_dev)."""
+    _same_numel("ops.adam_ema_dev", p, g, m, v, ema)
+    _lib.call("irgan_adam_ema_dev", P(p), P(g), P(m), P(v), P(ema), p.numel(), P(prm), ctypes.c_float(b1),
+              ctypes.c_float(b2), ctypes.c_float(eps), stream())
+
+
 # ----------------------------------------------------------------------------
 # fp8 (OCP e4m3) operands: BASELINE config 5
 # ----------------------------------------------------------------------------
