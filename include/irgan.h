@@ -538,6 +538,9 @@ IRGAN_API int irgan_ssim_ws(const float* a, const float* b, int32_t N, int32_t H
                   float* g, double* loss, float* work, int32_t window, irgan_stream_t s);
 
 /* ---- optimizer (torch.optim.Adam, ir:1601-1604) over a flat fp32 buffer ---- */
+/* Both families below take any 4-byte-aligned pointers and n >= 1: 16-byte accesses when the
+ * pointers of a call (p, g, m, v and, where there is one, ema) share one offset from a
+ * 16-byte boundary (scalar head / tail), one element per lane otherwise. */
 /* step_size = lr/(1-beta1^t), bc2_sqrt = sqrt(1-beta2^t) (host, fp64 -> fp32). */
 IRGAN_API int irgan_adam(float* p, const float* g, float* m, float* v, int64_t n, float step_size,
                float beta1, float beta2, float bc2_sqrt, float eps, irgan_stream_t s);
@@ -552,9 +555,7 @@ IRGAN_API int irgan_adam_dev(float* p, const float* g, float* m, float* v, int64
  * pass: per element, after the Adam update, ema += ema_weight * (p_new - ema).  p, m, v are
  * bit-identical to the plain entries.  ema_weight = 1 - min(decay, (1 + t) / (10 + t)) for
  * the 1-based step t (fp64 -> fp32); irgan_adam_ema_prep (decay in [0, 1), else
- * IRGAN_EINVAL) writes it to prm[2] beside prm[0], prm[1], so its prm holds THREE floats.
- * Any 4-byte-aligned pointers and n >= 1: 16-byte accesses when the five pointers share one
- * offset from a 16-byte boundary (scalar head / tail), one element per lane otherwise. */
+ * IRGAN_EINVAL) writes it to prm[2] beside prm[0], prm[1], so its prm holds THREE floats. */
 IRGAN_API int irgan_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float step_size,
                    float beta1, float beta2, float bc2_sqrt, float eps, float ema_weight, irgan_stream_t s);
 IRGAN_API int irgan_adam_ema_prep(int32_t* count, double lr, double beta1, double beta2, double ema_decay,

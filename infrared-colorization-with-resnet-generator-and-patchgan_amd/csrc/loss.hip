@@ -338,11 +338,11 @@ __global__ __launch_bounds__(TPB) void ssim_h_kernel(const float* __restrict__ i
 }
 
 // One element of torch.optim.Adam (ir:1601-1604): updates the moments in place and returns
-// the new parameter.  adam_kernel and the EMA kernels below all go through this one body, so
-// their p / m / v agree bit for bit -- which also needs every rounding pinned: left to the
-// compiler, the scalar and the 16-byte kernels contract a*b + c differently.  Contraction is
-// off in here and the fused operations are spelled out; they are the ones adam_kernel has
-// always compiled to (m and p one fma each, v two products and a sum).
+// the new parameter.  Every Adam kernel below goes through this one body, so their p / m / v
+// agree bit for bit -- which also needs every rounding pinned: left to the compiler, the
+// one-element and the 16-byte kernels contract a*b + c differently.  Contraction is off in
+// here and the fused operations are spelled out (m and p one fma each, v two products and a
+// sum).
 IRGAN_HD float adam_update(float pi, float gi, float& mi, float& vi, float step_size, float w1, float b2, float w2,
                            float bc2s, float eps) {
 #pragma clang fp contract(off)
@@ -360,109 +360,108 @@ IRGAN_HD float ema_update(float ei, float pn, float we) {
     return __builtin_fmaf(we, pn - ei, ei);
 }
 
-// prm (device, nullable): {step_size, bc2s} written by adam_prep_kernel in the same stream
-// (graph replay: the step count lives on the device, so a captured step stays valid)
-__global__ __launch_bounds__(TPB) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long n,
-                                                   float step_size, float b1, float b2, float bc2s, float eps,
-                                                   const float* __restrict__ prm = nullptr) {
-    if (prm) {
-        step_size = prm[0];
-        bc2s = prm[1];
-    }
-    const float w1 = 1.f - b1, w2 = 1.f - b2;
-    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) {
-        float mi = m[i], vi = v[i];
-        p[i] = adam_update(p[i], g[i], mi, vi, step_size, w1, b2, w2, bc2s, eps);
-        m[i] = mi;
-        v[i] = vi;
-    }
-}
-
-// Adam + the exponential moving average of the new parameters, e += we * (p_new - e), in the
-// same pass (5 reads, 4 writes per element).  prm (device, nullable): {step_size, bc2s, we}
-// from adam_ema_prep_kernel.
-struct AdamEmaArgs {
+// Adam (4 reads, 3 writes per element) and, with e (EMA), the exponential moving average of
+// the new parameters, e += we * (p_new - e), in the same pass (5 reads, 4 writes).
+// prm (device, nullable): {step_size, bc2s} and, EMA, {.., we}, written by adam_prep_kernel in
+// the same stream (graph replay: the step count lives on the device, so a captured step stays
+// valid).  Without EMA neither e nor prm[2] nor we is touched.
+struct AdamArgs {
     float *p, *m, *v, *e;
     const float* g;
     const float* prm;
     float step_size, b1, b2, bc2s, eps, we;
 };
 
-IRGAN_HD void adam_ema_coeffs(const AdamEmaArgs& a, float& step_size, float& bc2s, float& we) {
+template <bool EMA>
+IRGAN_HD void adam_coeffs(const AdamArgs& a, float& step_size, float& bc2s, float& we) {
     step_size = a.step_size, bc2s = a.bc2s, we = a.we;
     if (a.prm) {
         step_size = a.prm[0];
         bc2s = a.prm[1];
-        we = a.prm[2];
+        if (EMA) we = a.prm[2];
     }
 }
 
-IRGAN_HD void adam_ema_one(const AdamEmaArgs& a, long i, float step_size, float w1, float w2, float bc2s, float we) {
+template <bool EMA>
+IRGAN_HD void adam_one(const AdamArgs& a, long i, float step_size, float w1, float w2, float bc2s, float we) {
     float mi = a.m[i], vi = a.v[i];
-    const float ei = a.e[i];
+    const float ei = EMA ? a.e[i] : 0.f;
     const float pn = adam_update(a.p[i], a.g[i], mi, vi, step_size, w1, a.b2, w2, bc2s, a.eps);
     a.p[i] = pn;
     a.m[i] = mi;
     a.v[i] = vi;
-    a.e[i] = ema_update(ei, pn, we);
+    if (EMA) a.e[i] = ema_update(ei, pn, we);
 }
 
 // any 4-byte-aligned pointers: one element per thread and round
-__global__ __launch_bounds__(TPB) void adam_ema_kernel(AdamEmaArgs a, long n) {
+template <bool EMA>
+__global__ __launch_bounds__(TPB) void adam_kernel(AdamArgs a, long n) {
     float step_size, bc2s, we;
-    adam_ema_coeffs(a, step_size, bc2s, we);
+    adam_coeffs<EMA>(a, step_size, bc2s, we);
     const float w1 = 1.f - a.b1, w2 = 1.f - a.b2;
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB)
-        adam_ema_one(a, i, step_size, w1, w2, bc2s, we);
+        adam_one<EMA>(a, i, step_size, w1, w2, bc2s, we);
 }
 
-// The five pointers share one offset from a 16-byte boundary: `head` (< 4) leading elements
-// and the tail (< 4) one per thread (block 0), the nvec groups of four between them with
+// The pointers share one offset from a 16-byte boundary: `head` (< 4) leading elements and
+// the tail (< 4) one per thread (block 0), the nvec groups of four between them with
 // 16-byte loads and stores, grid-stride.  n = head + 4 * nvec + tail.
-__global__ __launch_bounds__(TPB) void adam_ema_vec_kernel(AdamEmaArgs a, int head, long nvec, int tail) {
+template <bool EMA>
+__global__ __launch_bounds__(TPB) void adam_vec_kernel(AdamArgs a, int head, long nvec, int tail) {
     float step_size, bc2s, we;
-    adam_ema_coeffs(a, step_size, bc2s, we);
+    adam_coeffs<EMA>(a, step_size, bc2s, we);
     const float w1 = 1.f - a.b1, w2 = 1.f - a.b2;
     float4* __restrict__ p4 = reinterpret_cast<float4*>(a.p + head);
     float4* __restrict__ m4 = reinterpret_cast<float4*>(a.m + head);
     float4* __restrict__ v4 = reinterpret_cast<float4*>(a.v + head);
-    float4* __restrict__ e4 = reinterpret_cast<float4*>(a.e + head);
+    float4* __restrict__ e4 = EMA ? reinterpret_cast<float4*>(a.e + head) : nullptr;
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(a.g + head);
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < nvec; i += (long)gridDim.x * TPB) {
-        float4 P = p4[i], M = m4[i], V = v4[i], E = e4[i];
+        float4 P = p4[i], M = m4[i], V = v4[i], E;
+        if (EMA) E = e4[i];
         const float4 G = g4[i];
         P.x = adam_update(P.x, G.x, M.x, V.x, step_size, w1, a.b2, w2, bc2s, a.eps);
         P.y = adam_update(P.y, G.y, M.y, V.y, step_size, w1, a.b2, w2, bc2s, a.eps);
         P.z = adam_update(P.z, G.z, M.z, V.z, step_size, w1, a.b2, w2, bc2s, a.eps);
         P.w = adam_update(P.w, G.w, M.w, V.w, step_size, w1, a.b2, w2, bc2s, a.eps);
-        E.x = ema_update(E.x, P.x, we);
-        E.y = ema_update(E.y, P.y, we);
-        E.z = ema_update(E.z, P.z, we);
-        E.w = ema_update(E.w, P.w, we);
+        if (EMA) {
+            E.x = ema_update(E.x, P.x, we);
+            E.y = ema_update(E.y, P.y, we);
+            E.z = ema_update(E.z, P.z, we);
+            E.w = ema_update(E.w, P.w, we);
+        }
         p4[i] = P;
         m4[i] = M;
         v4[i] = V;
-        e4[i] = E;
+        if (EMA) e4[i] = E;
     }
     if (blockIdx.x == 0 && (int)threadIdx.x < head + tail) {
         const int t = threadIdx.x;
-        adam_ema_one(a, t < head ? (long)t : (long)head + 4 * nvec + (t - head), step_size, w1, w2, bc2s, we);
+        adam_one<EMA>(a, t < head ? (long)t : (long)head + 4 * nvec + (t - head), step_size, w1, w2, bc2s, we);
     }
 }
 
-// The vector kernel takes one group of four per thread under nblocks' cap: a full round of
-// its grid is 8192 * TPB * 4 elements, the rest grid-strides.
-int adam_ema_launch(const AdamEmaArgs& a, long n, hipStream_t st) {
+// EMA iff a.e.  16-byte accesses when the pointers that exist (four, with EMA five) share one
+// offset from a 16-byte boundary and there is a whole group of four; one element per lane
+// otherwise.  The vector kernel takes one group of four per thread under nblocks' cap: a full
+// round of its grid is 8192 * TPB * 4 elements, the rest grid-strides.
+int adam_launch(const AdamArgs& a, long n, hipStream_t st) {
     const uintptr_t off = (uintptr_t)a.p % 16;
-    const bool same = (uintptr_t)a.g % 16 == off && (uintptr_t)a.m % 16 == off && (uintptr_t)a.v % 16 == off &&
-                      (uintptr_t)a.e % 16 == off && off % 4 == 0;
+    auto at_off = [off](const float* q) { return (uintptr_t)q % 16 == off; };
+    const bool same = at_off(a.g) && at_off(a.m) && at_off(a.v) && (!a.e || at_off(a.e)) && off % 4 == 0;
     const long head = std::min<long>(n, (16 - (long)off) % 16 / 4);
     const long nvec = (n - head) / 4;
-    if (same && nvec > 0)
-        adam_ema_vec_kernel<<<nblocks(nvec), TPB, 0, st>>>(a, (int)head, nvec, (int)(n - head - 4 * nvec));
-    else
-        adam_ema_kernel<<<nblocks(n), TPB, 0, st>>>(a, n);
+    const int tail = (int)(n - head - 4 * nvec);
+    if (same && nvec > 0) {
+        if (a.e)
+            adam_vec_kernel<true><<<nblocks(nvec), TPB, 0, st>>>(a, (int)head, nvec, tail);
+        else
+            adam_vec_kernel<false><<<nblocks(nvec), TPB, 0, st>>>(a, (int)head, nvec, tail);
+    } else if (a.e) {
+        adam_kernel<true><<<nblocks(n), TPB, 0, st>>>(a, n);
+    } else {
+        adam_kernel<false><<<nblocks(n), TPB, 0, st>>>(a, n);
+    }
     IRGAN_LAUNCH_CHECK();
     return 0;
 }
@@ -610,17 +609,14 @@ extern "C" int irgan_adam_dev(float* p, const float* g, float* m, float* v, int6
                               float beta2, float eps, irgan_stream_t s) {
     if (!prm) return IRGAN_EINVAL;
     if (n <= 0) return 0;
-    adam_kernel<<<nblocks(n), TPB, 0, (hipStream_t)s>>>(p, g, m, v, n, 0.f, beta1, beta2, 1.f, eps, prm);
-    IRGAN_LAUNCH_CHECK();
-    return 0;
+    return adam_launch(AdamArgs{p, m, v, nullptr, g, prm, 0.f, beta1, beta2, 1.f, eps, 0.f}, n, (hipStream_t)s);
 }
 
 extern "C" int irgan_adam(float* p, const float* g, float* m, float* v, int64_t n, float step_size, float beta1,
                           float beta2, float bc2_sqrt, float eps, irgan_stream_t s) {
     if (n <= 0) return 0;
-    adam_kernel<<<nblocks(n), TPB, 0, (hipStream_t)s>>>(p, g, m, v, n, step_size, beta1, beta2, bc2_sqrt, eps);
-    IRGAN_LAUNCH_CHECK();
-    return 0;
+    return adam_launch(AdamArgs{p, m, v, nullptr, g, nullptr, step_size, beta1, beta2, bc2_sqrt, eps, 0.f}, n,
+                       (hipStream_t)s);
 }
 
 extern "C" int irgan_adam_ema_prep(int32_t* count, double lr, double beta1, double beta2, double ema_decay, float* prm,
@@ -635,13 +631,13 @@ extern "C" int irgan_adam_ema_dev(float* p, const float* g, float* m, float* v, 
                                   float beta1, float beta2, float eps, irgan_stream_t s) {
     if (!prm || !ema) return IRGAN_EINVAL;
     if (n <= 0) return 0;
-    return adam_ema_launch(AdamEmaArgs{p, m, v, ema, g, prm, 0.f, beta1, beta2, 1.f, eps, 0.f}, n, (hipStream_t)s);
+    return adam_launch(AdamArgs{p, m, v, ema, g, prm, 0.f, beta1, beta2, 1.f, eps, 0.f}, n, (hipStream_t)s);
 }
 
 extern "C" int irgan_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float step_size,
                               float beta1, float beta2, float bc2_sqrt, float eps, float ema_weight, irgan_stream_t s) {
     if (!ema) return IRGAN_EINVAL;
     if (n <= 0) return 0;
-    return adam_ema_launch(AdamEmaArgs{p, m, v, ema, g, nullptr, step_size, beta1, beta2, bc2_sqrt, eps, ema_weight},
+    return adam_launch(AdamArgs{p, m, v, ema, g, nullptr, step_size, beta1, beta2, bc2_sqrt, eps, ema_weight},
                            n, (hipStream_t)s);
 }

@@ -160,7 +160,7 @@ class ParamStore:
         self.ema = None         # enable_ema(): the parameters' moving average, updated by Adam's pass
         self.step_count = 0
         self.dev_adam = False   # GANStep: step count on the device (irgan_adam_prep)
-        self._count = self._prm = self._prm_ema = None
+        self._count = self._prm = None
         self._count_host = 0
 
     def krsc(self, k, buf=None):
@@ -267,8 +267,7 @@ class ParamStore:
         bucket's gradient all-reduce completes (BucketedAllreduce.finish).  With ``ema_decay``
         and an ``ema`` buffer the same launch also moves ema[start:end] towards the new
         parameters (ops.ema_weight); otherwise ``ema`` is not touched."""
-        if ema_decay and self.ema is not None:
-            return self._adam_ema_begin(lr, b1, b2, eps, ema_decay)
+        ema = self.ema if ema_decay else None
         self.step_count += 1
         t = self.step_count
         if self.dev_adam:
@@ -276,47 +275,21 @@ class ParamStore:
             # the right t); the device count is resynced to the host's after a state load
             if self._count is None:
                 self._count = torch.zeros(1, dtype=torch.int32, device=self.device)
-                self._prm = torch.zeros(2, dtype=torch.float32, device=self.device)
+                self._prm = torch.zeros(3, dtype=torch.float32, device=self.device)  # the third: EMA weight
                 self._count_host = 0
             if self._count_host != t - 1:
                 self._count.fill_(t - 1)
-            ops.adam_prep(self._count, lr, b1, b2, self._prm)
+            ops.adam_prep(self._count, lr, b1, b2, self._prm, None if ema is None else ema_decay)
             self._count_host = t
 
             def apply_dev(a, b):
-                ops.adam_dev(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], self._prm, b1, b2, eps)
+                ops.adam_dev(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], self._prm, b1, b2, eps,
+                             None if ema is None else ema[a:b])
             return apply_dev
 
         def apply(a, b):
-            ops.adam(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], t, lr, b1, b2, eps)
-        return apply
-
-    def _adam_ema_begin(self, lr, b1, b2, eps, decay):
-        """adam_begin's two paths on the EMA kernels.  The device count is the one the plain
-        path uses; the parameter block is this path's own three floats (the plain entries'
-        prm stays two)."""
-        self.step_count += 1
-        t = self.step_count
-        if self.dev_adam:
-            if self._count is None:
-                self._count = torch.zeros(1, dtype=torch.int32, device=self.device)
-                self._prm = torch.zeros(2, dtype=torch.float32, device=self.device)
-                self._count_host = 0
-            if self._prm_ema is None:
-                self._prm_ema = torch.zeros(3, dtype=torch.float32, device=self.device)
-            if self._count_host != t - 1:
-                self._count.fill_(t - 1)
-            ops.adam_ema_prep(self._count, lr, b1, b2, decay, self._prm_ema)
-            self._count_host = t
-
-            def apply_dev(a, b):
-                ops.adam_ema_dev(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], self.ema[a:b],
-                                 self._prm_ema, b1, b2, eps)
-            return apply_dev
-
-        def apply(a, b):
-            ops.adam_ema(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], self.ema[a:b], t, lr, b1, b2,
-                         eps, decay)
+            ops.adam(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], t, lr, b1, b2, eps,
+                     None if ema is None else ema[a:b], ema_decay)
         return apply
 
 

@@ -1104,26 +1104,6 @@ def ssim(a: Feat, b: Feat, w: float, g: torch.Tensor, loss: torch.Tensor, work: 
               stream())
 
 
-def adam(p, g, m, v, step: int, lr: float, b1: float, b2: float, eps: float):
-    bc1 = 1 - b1 ** step
-    bc2 = 1 - b2 ** step
-    _lib.call("irgan_adam", P(p), P(g), P(m), P(v), p.numel(), ctypes.c_float(lr / bc1), ctypes.c_float(b1),
-              ctypes.c_float(b2), ctypes.c_float(math.sqrt(bc2)), ctypes.c_float(eps), stream())
-
-
-def adam_prep(count: torch.Tensor, lr: float, b1: float, b2: float, prm: torch.Tensor):
-    """Device-side step count + bias corrections (irgan_adam_prep): count (int32[1]) += 1,
-    prm (fp32[2]) = {lr / (1 - b1^t), sqrt(1 - b2^t)} -- ops.adam's host formula."""
-    _lib.call("irgan_adam_prep", P(count), ctypes.c_double(lr), ctypes.c_double(b1), ctypes.c_double(b2), P(prm),
-              stream())
-
-
-def adam_dev(p, g, m, v, prm: torch.Tensor, b1: float, b2: float, eps: float):
-    """ops.adam with step_size / bc2_sqrt read from prm on the device (irgan_adam_dev)."""
-    _lib.call("irgan_adam_dev", P(p), P(g), P(m), P(v), p.numel(), P(prm), ctypes.c_float(b1), ctypes.c_float(b2),
-              ctypes.c_float(eps), stream())
-
-
 def ema_weight(decay: float, t: int) -> float:
     """The weight of the new parameters in the EMA update after optimizer step ``t`` (1-based):
     ``1 - min(decay, (1 + t) / (10 + t))``, so ``e += w * (p - e)``.  The warm-up term lets a
@@ -1132,36 +1112,42 @@ def ema_weight(decay: float, t: int) -> float:
     return 1.0 - min(float(decay), (1.0 + t) / (10.0 + t))
 
 
-def _same_numel(what, p, *others):
-    if any(t.numel() != p.numel() for t in others):
-        raise ValueError(f"{what}: p, g, m, v and ema must have one element count")
+def _adam_call(form, p, g, m, v, ema, *args):
+    """irgan_adam<form> or, with ``ema``, irgan_adam_ema<form>, which takes it after ``v``."""
+    if ema is None:
+        return _lib.call(f"irgan_adam{form}", P(p), P(g), P(m), P(v), p.numel(), *args, stream())
+    if any(t.numel() != p.numel() for t in (g, m, v, ema)):
+        raise ValueError(f"ops.adam{form}: p, g, m, v and ema must have one element count")
+    _lib.call(f"irgan_adam_ema{form}", P(p), P(g), P(m), P(v), P(ema), p.numel(), *args, stream())
 
 
-def adam_ema(p, g, m, v, ema, step: int, lr: float, b1: float, b2: float, eps: float, decay: float):
-    """ops.adam and, in the same pass, ema += ema_weight(decay, step) * (p_new - ema)
-    (irgan_adam_ema); p, m, v come out as ops.adam leaves them, bit for bit."""
-    _same_numel("ops.adam_ema", p, g, m, v, ema)
+def adam(p, g, m, v, step: int, lr: float, b1: float, b2: float, eps: float, ema=None, decay: float = 0.0):
+    """One Adam step with host-side bias corrections (irgan_adam).  With ``ema`` also, in the
+    same pass, ema += ema_weight(decay, step) * (p_new - ema) (irgan_adam_ema); p, m, v come
+    out the same with and without it, bit for bit."""
     bc1 = 1 - b1 ** step
     bc2 = 1 - b2 ** step
-    _lib.call("irgan_adam_ema", P(p), P(g), P(m), P(v), P(ema), p.numel(), ctypes.c_float(lr / bc1),
-              ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(math.sqrt(bc2)), ctypes.c_float(eps),
-              ctypes.c_float(ema_weight(decay, step)), stream())
+    tail = () if ema is None else (ctypes.c_float(ema_weight(decay, step)),)
+    _adam_call("", p, g, m, v, ema, ctypes.c_float(lr / bc1), ctypes.c_float(b1), ctypes.c_float(b2),
+               ctypes.c_float(math.sqrt(bc2)), ctypes.c_float(eps), *tail)
 
 
-def adam_ema_prep(count: torch.Tensor, lr: float, b1: float, b2: float, decay: float, prm: torch.Tensor):
-    """ops.adam_prep with prm (fp32[3]) = {step_size, bc2_sqrt, ema_weight(decay, t)}
-    (irgan_adam_ema_prep)."""
+def adam_prep(count: torch.Tensor, lr: float, b1: float, b2: float, prm: torch.Tensor, decay: float = None):
+    """Device-side step count + bias corrections (irgan_adam_prep): count (int32[1]) += 1,
+    prm[:2] = {lr / (1 - b1^t), sqrt(1 - b2^t)} -- ops.adam's host formula.  With ``decay``
+    also prm[2] = ema_weight(decay, t), so prm holds three floats (irgan_adam_ema_prep)."""
+    lrb = (ctypes.c_double(lr), ctypes.c_double(b1), ctypes.c_double(b2))
+    if decay is None:
+        return _lib.call("irgan_adam_prep", P(count), *lrb, P(prm), stream())
     if prm.numel() < 3:
-        raise ValueError("ops.adam_ema_prep: prm holds three floats")
-    _lib.call("irgan_adam_ema_prep", P(count), ctypes.c_double(lr), ctypes.c_double(b1), ctypes.c_double(b2),
-              ctypes.c_double(decay), P(prm), stream())
+        raise ValueError("ops.adam_prep: with decay, prm holds three floats")
+    _lib.call("irgan_adam_ema_prep", P(count), *lrb, ctypes.c_double(decay), P(prm), stream())
 
 
-def adam_ema_dev(p, g, m, v, ema, prm: torch.Tensor, b1: float, b2: float, eps: float):
-    """ops.adam_ema with step_size / bc2_sqrt / the EMA weight read from prm (irgan_adam_ema_dev)."""
-    _same_numel("ops.adam_ema_dev", p, g, m, v, ema)
-    _lib.call("irgan_adam_ema_dev", P(p), P(g), P(m), P(v), P(ema), p.numel(), P(prm), ctypes.c_float(b1),
-              ctypes.c_float(b2), ctypes.c_float(eps), stream())
+def adam_dev(p, g, m, v, prm: torch.Tensor, b1: float, b2: float, eps: float, ema=None):
+    """ops.adam with step_size / bc2_sqrt and, with ``ema``, the EMA weight read from prm on the
+    device (irgan_adam_dev / irgan_adam_ema_dev)."""
+    _adam_call("_dev", p, g, m, v, ema, P(prm), ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(eps))
 
 
 # ----------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""Config.ema_decay on the GPU: the fused Adam + EMA kernels against the plain Adam kernel
-(bit for bit) and an fp64 recurrence, the unchanged step, the bucketed (data-parallel) path,
-resume, GANTrainer.ema_weights() and train_kaist's EMA files.
+"""Config.ema_decay on the GPU: the Adam kernels with EMA against those without (bit for bit)
+and an fp64 recurrence, the plain entries off 16-byte alignment, ParamStore.adam_begin's one
+path, the unchanged step, the bucketed (data-parallel) path, resume, GANTrainer.ema_weights()
+and train_kaist's EMA files.
 
 The EMA bound used throughout: e' = e + w (p - e) in fp32 is at most four roundings in either
 lerp form, each relative to a quantity <= |e| + |p|, i.e. 4 * 2^-24 = 2^-22 of it; the tests
@@ -19,9 +20,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LR, B1, B2, EPS, DECAY = 2e-4, 0.5, 0.999, 1e-8, 0.999
 SEED = 1234
-# the vector kernel's launch geometry (csrc/loss.hip: adam_ema_vec_kernel under nblocks' cap):
-# at most 8192 blocks x 256 threads x 4 elements per round, the rest grid-strides
-FULL_ROUND = 8192 * 256 * 4
+# the launch geometry (csrc/loss.hip: adam_launch under nblocks' cap): at most 8192 blocks x 256
+# threads per round, x 4 elements in the vector kernel; the rest grid-strides
+SCALAR_ROUND = 8192 * 256
+FULL_ROUND = SCALAR_ROUND * 4
+PAD = 8   # floats each _views allocation holds beyond its view
 
 
 @pytest.fixture(autouse=True)
@@ -52,12 +55,12 @@ def _w32(t, decay=DECAY):
 # ---------------------------------------------------------------------------------------------
 
 def _views(n, offs, gen):
-    """Five randn vectors of n elements, each a view starting offs[i] elements into its own
-    allocation (the allocator's blocks are 512-byte aligned, so offs[i] % 4 is the pointer's
-    offset from a 16-byte boundary in floats)."""
+    """One randn vector of n elements per offset, each a view starting offs[i] elements into
+    its own zeroed allocation of n + PAD (the allocator's blocks are 512-byte aligned, so
+    offs[i] % 4 is the pointer's offset from a 16-byte boundary in floats)."""
     out = []
     for o in offs:
-        base = torch.zeros(n + 8, device=DEV)
+        base = torch.zeros(n + PAD, device=DEV)
         v = base[o:o + n]
         v.copy_(torch.randn(n, generator=gen).to(DEV))
         assert v.data_ptr() % 16 == 4 * (o % 4)
@@ -65,12 +68,24 @@ def _views(n, offs, gen):
     return out
 
 
+def _padding_is_zero(view):
+    """The PAD floats of a _views allocation outside the view: nothing was written there."""
+    base, o = view._base, view.storage_offset()
+    assert base.numel() == view.numel() + PAD
+    return not bool(base[:o].any()) and not bool(base[o + view.numel():].any())
+
+
+TINY = [(1, 1), (5, 3), (6, 2), (10, 1)]   # fallback (nvec == 0); head 1; head 2; head 3 and tail 3
+TINY_IDS = ["n1_off1", "n5_off3", "n6_off2", "n10_off1"]
+
+
 @pytest.mark.parametrize("n,offs", [
     (1, (0,) * 5), (63, (0,) * 5), (1001, (0,) * 5),
     (FULL_ROUND + 1001, (0,) * 5),                       # a full round of the grid + a ragged second one
     (1001, (1,) * 5), (1001, (2,) * 5), (1001, (3,) * 5),  # shared misalignment: scalar head, vector body
     (1001, (0, 1, 2, 3, 1)),                             # no common offset: the one-element-per-lane kernel
-], ids=["n1", "n63", "n1001", "full_round_plus_1001", "off1", "off2", "off3", "mixed_offsets"])
+] + [(n, (o,) * 5) for n, o in TINY],
+    ids=["n1", "n63", "n1001", "full_round_plus_1001", "off1", "off2", "off3", "mixed_offsets"] + TINY_IDS)
 def test_adam_ema_kernels_vs_adam_and_fp64(n, offs):
     ops = pkg().ops
     gen = torch.Generator().manual_seed(n + 7 * sum(offs))
@@ -90,17 +105,17 @@ def test_adam_ema_kernels_vs_adam_and_fp64(n, offs):
     for t in (1, 2, 3):
         g.copy_(torch.randn(n, generator=gen).to(DEV))
         e_prev = e.clone()
-        ops.adam_ema_prep(cnt, LR, B1, B2, DECAY, prm)
-        ops.adam_ema_dev(p, g, m, v, e, prm, B1, B2, EPS)
+        ops.adam_prep(cnt, LR, B1, B2, prm, decay=DECAY)
+        ops.adam_dev(p, g, m, v, prm, B1, B2, EPS, ema=e)
         ops.adam(pa, g, ma, va, t, LR, B1, B2, EPS)
         ops.adam_prep(cnt_b, LR, B1, B2, prm_b)
         ops.adam_dev(pb, g, mb, vb, prm_b, B1, B2, EPS)
-        ops.adam_ema(ph, g, mh, vh, eh, t, LR, B1, B2, EPS, DECAY)
+        ops.adam(ph, g, mh, vh, t, LR, B1, B2, EPS, ema=eh, decay=DECAY)
         torch.cuda.synchronize()
         for name, got, a, b, h in (("p", p, pa, pb, ph), ("m", m, ma, mb, mh), ("v", v, va, vb, vh)):
             assert torch.equal(got, a), (name, t, "vs ops.adam")
             assert torch.equal(got, b), (name, t, "vs ops.adam_prep + ops.adam_dev")
-            assert torch.equal(got, h), (name, t, "vs ops.adam_ema")
+            assert torch.equal(got, h), (name, t, "vs ops.adam with ema")
         # the device-side count and weight
         assert int(cnt.item()) == t and int(cnt_b.item()) == t
         want = _w32(t)
@@ -117,7 +132,7 @@ def test_adam_ema_kernels_vs_adam_and_fp64(n, offs):
         err_wrong = (e.double() - _ema_ref(e_prev, p, _w32(t + 1))).abs()
         assert not (err_wrong <= bound).all(), (t, "the check cannot tell w_t from w_t+1")
         # host arguments = device count, bit for bit
-        assert torch.equal(e, eh), (t, "ops.adam_ema vs ops.adam_ema_dev")
+        assert torch.equal(e, eh), (t, "ops.adam with ema vs ops.adam_dev with ema")
         if t == 1:
             # every element was visited, tail included.  An element whose exact update is below
             # the rounding bound may legitimately keep its value (p and e are independent
@@ -128,16 +143,117 @@ def test_adam_ema_kernels_vs_adam_and_fp64(n, offs):
             assert int((~movable).sum()) <= max(0, n // 100000), int((~movable).sum())
             if n <= 1001:
                 assert (e != e0).all()
+    # nothing was written outside [0, n)
+    for name, x in (("p", p), ("m", m), ("v", v), ("e", e)):
+        assert _padding_is_zero(x), name
 
 
 def test_adam_ema_binding_refuses_mismatched_sizes():
     ops = pkg().ops
     x = [torch.zeros(8, device=DEV) for _ in range(4)]
     with pytest.raises(ValueError):
-        ops.adam_ema(*x, torch.zeros(7, device=DEV), 1, LR, B1, B2, EPS, DECAY)
+        ops.adam(*x, 1, LR, B1, B2, EPS, ema=torch.zeros(7, device=DEV), decay=DECAY)
     with pytest.raises(ValueError):
-        ops.adam_ema_prep(torch.zeros(1, dtype=torch.int32, device=DEV), LR, B1, B2, DECAY,
-                          torch.zeros(2, device=DEV))
+        ops.adam_prep(torch.zeros(1, dtype=torch.int32, device=DEV), LR, B1, B2, torch.zeros(2, device=DEV),
+                      decay=DECAY)
+
+
+# |p - torch.optim.Adam on the CPU| after three steps: the project's Adam bound
+# (tests/test_gpu_losses.py: the same hyper-parameters, randn parameters and gradients)
+ADAM_BOUND = 5e-7
+
+
+@pytest.mark.parametrize("n,offs", [(n, (o,) * 4) for n, o in TINY] + [
+    (1001, (1,) * 4), (1001, (2,) * 4), (1001, (3,) * 4),
+    (1001, (0, 1, 2, 3)),                   # no common offset: the one-element-per-lane kernel
+    (SCALAR_ROUND + 1001, (0, 1, 2, 3)),    # ... and a second, ragged round of it
+], ids=TINY_IDS + ["off1", "off2", "off3", "mixed_offsets", "mixed_offsets_second_round"])
+def test_plain_adam_offsets(n, offs):
+    """The plain entries off alignment (head / 16-byte body / tail, and the fallback): bit-equal
+    to the same update on aligned clones and to the EMA entry's p / m / v on the same views."""
+    ops = pkg().ops
+    gen = torch.Generator().manual_seed(n + 7 * sum(offs))
+    p, m, v, g = _views(n, offs, gen)
+    m.zero_()
+    v.zero_()
+    pa, ma, va = p.clone(), m.clone(), v.clone()      # aligned, ops.adam
+    pb, mb, vb = p.clone(), m.clone(), v.clone()      # aligned, device count
+    # the EMA entry on offset views of its own (e at p's offset)
+    pe, me, ve, ee = _views(n, offs[:3] + offs[:1], gen)
+    pe.copy_(p)
+    me.zero_()
+    ve.zero_()
+    pt = p.cpu().clone().requires_grad_(True)
+    opt = torch.optim.Adam([pt], lr=LR, betas=(B1, B2), eps=EPS)
+    cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
+    prm = torch.zeros(2, device=DEV)
+    for t in (1, 2, 3):
+        gr = torch.randn(n, generator=gen)
+        g.copy_(gr.to(DEV))
+        pt.grad = gr
+        opt.step()
+        ops.adam(p, g, m, v, t, LR, B1, B2, EPS)
+        ops.adam(pa, g, ma, va, t, LR, B1, B2, EPS)
+        ops.adam_prep(cnt, LR, B1, B2, prm)
+        ops.adam_dev(pb, g, mb, vb, prm, B1, B2, EPS)
+        ops.adam(pe, g, me, ve, t, LR, B1, B2, EPS, ema=ee, decay=DECAY)
+        torch.cuda.synchronize()
+        for name, got, a, b, e in (("p", p, pa, pb, pe), ("m", m, ma, mb, me), ("v", v, va, vb, ve)):
+            assert torch.equal(got, a), (name, t, "vs ops.adam on aligned clones")
+            assert torch.equal(got, b), (name, t, "vs ops.adam_prep + ops.adam_dev on aligned clones")
+            assert torch.equal(got, e), (name, t, "vs the EMA entry on the same offsets")
+        if t == 1:
+            assert bool((m != 0).all())   # every element was visited, head and tail included
+    err = float((p.cpu() - pt.detach()).abs().max())
+    print(f"n={n} offs={offs}: max |p - torch.optim.Adam| / bound = {err / ADAM_BOUND:.3f}")
+    assert err < ADAM_BOUND
+    for name, x in (("p", p), ("m", m), ("v", v), ("g", g)):
+        assert _padding_is_zero(x), name
+
+
+LAYOUT = {"a.weight": (5, 3, 3, 3), "a.bias": (5,), "b.weight": (7, 5, 1, 1)}
+
+
+@pytest.mark.parametrize("decay", [DECAY, 0.0], ids=["ema", "plain"])
+def test_paramstore_one_path(decay):
+    """ParamStore.adam_begin with the step count on the device and on the host, applied whole
+    and in two spans, with and without EMA, across a state load: one result."""
+    ParamStore = pkg().engine.ParamStore
+    gen = torch.Generator().manual_seed(5)
+    dev, host = ParamStore(LAYOUT, DEV), ParamStore(LAYOUT, DEV)
+    dev.dev_adam = True
+    n = dev.numel
+    cut = 192   # a.weight's 135 elements fill slices of 64 up to here
+    assert n == host.numel and 0 < cut < n and cut % 64 == 0 and cut == dev.offsets["a.bias"]
+    init = torch.randn(n, generator=gen).to(DEV)
+    for s in (dev, host):
+        s.flat.copy_(init)
+        s.enable_ema()
+    ema0 = init.clone()
+
+    def step():
+        gr = torch.randn(n, generator=gen).to(DEV)
+        dev.grad.copy_(gr)
+        host.grad.copy_(gr)
+        dev.adam_begin(LR, B1, B2, EPS, ema_decay=decay)(0, n)
+        apply = host.adam_begin(LR, B1, B2, EPS, ema_decay=decay)
+        apply(0, cut)
+        apply(cut, n)
+        torch.cuda.synchronize()
+        for name in ("flat", "m", "v", "ema"):
+            assert torch.equal(getattr(dev, name), getattr(host, name)), (name, dev.step_count)
+
+    for _ in range(3):
+        step()
+    assert int(dev._count.item()) == 3 and dev.step_count == host.step_count == 3
+    assert not torch.equal(dev.flat, init)
+    dev.step_count = host.step_count = 7   # as load_adam_state_dict leaves it
+    step()
+    assert int(dev._count.item()) == 8 and dev.step_count == host.step_count == 8
+    if decay:
+        assert not torch.equal(dev.ema, ema0)
+    else:
+        assert torch.equal(dev.ema, ema0) and torch.equal(host.ema, ema0)
 
 
 # ---------------------------------------------------------------------------------------------

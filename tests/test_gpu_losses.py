@@ -56,7 +56,8 @@ L1, ``ops.l1`` on views one element into their storage, count % 8 == 0: the alig
   a second, ragged round.  fp32 and bf16 operands, fp32 and bf16 ga, accumulate into a bf16 ga.
   Bounds of test_l1_bf16_features_tight.
 
-Adam, n = 8192 * 256 + 1001: a second, ragged round of adam_kernel's grid-stride loop.  Three steps
+Adam, n = 8192 * 256 * 4 + 1001: a second, ragged round of the grid-stride loop of the 16-byte kernel
+  these aligned tensors take (the one-element-per-lane kernel's: tests/test_gpu_ema.py).  Three steps
   of ``ops.adam`` and of ``ops.adam_prep`` + ``ops.adam_dev`` vs torch.optim.Adam on the CPU (5e-7 on
   p); m and v equal between the variants; the device step count is 3; prm within one fp32 ulp of the
   host's fp64 formula.
@@ -313,7 +314,7 @@ def test_l1_misaligned_views_take_the_scalar_kernel(ops, dt, gdt, accumulate):
 # ----------------------------------------------------------------------------
 
 def test_adam_second_round_host_and_device_step_count(ops):
-    n = 8192 * 256 + 1001
+    n = 8192 * 256 * 4 + 1001
     lr, b1, b2, eps = 2e-4, 0.5, 0.999, 1e-8
     gen = torch.Generator().manual_seed(41)
     p = torch.randn(n, generator=gen)
@@ -345,4 +346,9 @@ def test_adam_second_round_host_and_device_step_count(ops):
     report("adam", host_err_over_bound=eh / 5e-7, dev_err_over_bound=ed / 5e-7, prm_ulps=worst_ulp)
     assert eh < 5e-7 and ed < 5e-7
     assert torch.equal(mh, md) and torch.equal(vh, vd)
-    assert bool((mh != 0).all())   # every element was visited, the ragged tail included
+    # every element was visited, the ragged tail included.  m alone cannot tell at this n: it
+    # cancels to an exact zero where g_3 == -m_2 (element 1621412 of this seed, in the CPU's fp32
+    # arithmetic as well), so such an element shows its visit by v, which only three zero
+    # gradients would leave at zero
+    assert bool(((mh != 0) | (vh != 0)).all())
+    assert int((mh == 0).sum()) <= n // 10 ** 6

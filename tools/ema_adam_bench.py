@@ -3,9 +3,9 @@
 Kernel timing, on G's flat parameter count, HIP events around blocks of launches, the three
 forms interleaved block by block and the median block taken:
 
-    (a) irgan_adam_dev                       the plain update (7 streams: 4 reads, 3 writes)
-    (b) irgan_adam_ema_dev                   Adam + EMA in one pass (9 streams: 5 reads, 4 writes)
-    (c) irgan_adam_dev + torch.lerp_         the unfused pair (10 streams and two launches)
+    (a) ops.adam_dev                         the plain update (7 streams: 4 reads, 3 writes)
+    (b) ops.adam_dev(..., ema=e)             Adam + EMA in one pass (9 streams: 5 reads, 4 writes)
+    (c) ops.adam_dev + torch.lerp_           the unfused pair (10 streams and two launches)
 
 each over a rotation of buffer sets larger than the 256 MiB Infinity Cache ("hbm": what the
 step sees, its other kernels having swept the caches) and on one set over and over ("hot").
@@ -50,14 +50,14 @@ def kernel_times(irc, n, sets, iters, rounds, warmup):
     prm2, prm3 = torch.zeros(2, device="cuda"), torch.zeros(3, device="cuda")
     ops.adam_prep(cnt, LR, B1, B2, prm2)
     cnt.zero_()
-    ops.adam_ema_prep(cnt, LR, B1, B2, DECAY, prm3)
+    ops.adam_prep(cnt, LR, B1, B2, prm3, decay=DECAY)
     w = ops.ema_weight(DECAY, 1)
 
     def form_a(b):
         ops.adam_dev(b["p"], b["g"], b["m"], b["v"], prm2, B1, B2, EPS)
 
     def form_b(b):
-        ops.adam_ema_dev(b["p"], b["g"], b["m"], b["v"], b["e"], prm3, B1, B2, EPS)
+        ops.adam_dev(b["p"], b["g"], b["m"], b["v"], prm3, B1, B2, EPS, ema=b["e"])
 
     def form_c(b):
         ops.adam_dev(b["p"], b["g"], b["m"], b["v"], prm2, B1, B2, EPS)
