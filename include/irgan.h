@@ -617,6 +617,33 @@ IRGAN_API int irgan_u8_to_unit(const void* in, int32_t N, int64_t per_image, con
 IRGAN_API int irgan_u8_native_to_unit(const void* src, int32_t N, int32_t H, int32_t W, int32_t C, int64_t img_stride,
                             const void* flip, int32_t max_rule, int32_t* img_max, float* out, void* out_u8,
                             irgan_stream_t s);
+/* Config.load_size, the paired random-crop jitter: "resize to the load size, keep a random
+ * window of the training size", the window alone computed.  Each entry is the one above it
+ * by name with three additions: crop, a device array [N][2] = {oy, ox} (int32, required),
+ * the window's top-left corner in image n's load-size image; Hload, Wload, the extents the
+ * tables describe (the Hout / Wout of the plain entry); Hout, Wout, the window's extents,
+ * which are those of out_u8 / out.  Output pixel (y, x) is pixel (y + oy, x + ox) of what
+ * the plain entry computes at Hload x Wload, bit for bit; flip mirrors the window (column
+ * Wout - 1 - x) and img_max is the max over the window's bytes alone (the IR rule of ir:1142
+ * sees the sample, not the load-size image).  The caller keeps 0 <= oy <= Hload - Hout and
+ * 0 <= ox <= Wload - Wout (data.DeviceResizer checks the batch on the host before it is
+ * uploaded); a null crop, Hout > Hload or Wout > Wload is IRGAN_EINVAL.
+ * irgan_u8_native_crop_to_unit: the load size is the source size (src [N][Hload][Wload][C]),
+ * nothing is resampled: the window's rows are read out of the source in place. */
+IRGAN_API int irgan_area_resize_crop_u8(const void* src, int32_t N, int32_t Hin, int32_t Win, int32_t C,
+                              int64_t img_stride, const int32_t* yptr, const int32_t* ysrc, const float* yw,
+                              int32_t Hload, const int32_t* xptr, const int32_t* xsrc, const float* xw,
+                              int32_t Wload, const int32_t* crop, int32_t Hout, int32_t Wout,
+                              const void* flip, void* out_u8, int32_t* img_max, irgan_stream_t s);
+IRGAN_API int irgan_linear_area_resize_crop_u8(const void* src, int32_t N, int32_t Hin, int32_t Win, int32_t C,
+                                     int64_t img_stride, const int32_t* yofs, const int32_t* ycoef,
+                                     int32_t Hload, const int32_t* xofs, const int32_t* xcoef, int32_t xlim,
+                                     int32_t Wload, const int32_t* crop, int32_t Hout, int32_t Wout,
+                                     const void* flip, void* out_u8, int32_t* img_max, irgan_stream_t s);
+IRGAN_API int irgan_u8_native_crop_to_unit(const void* src, int32_t N, int32_t Hload, int32_t Wload, int32_t C,
+                                 int64_t img_stride, const int32_t* crop, int32_t Hout, int32_t Wout,
+                                 const void* flip, int32_t max_rule, int32_t* img_max, float* out,
+                                 void* out_u8, irgan_stream_t s);
 
 /* The SSIM of compute_metrics (ir:1208-1213): skimage.metrics.structural_similarity(
  * gt, pred, data_range=1.0, channel_axis=2) for N uint8 image pairs [N][H][W][C]

@@ -1,13 +1,16 @@
 """``python -m infrared-colorization-with-resnet-generator-and-patchgan_amd [train|test]
-[--img-size N | HxW | native] [--ema-decay D]`` -- the reference's script entry point (ir:1730-1756) with
-cfg.mode taken from the command line (default: Config's "test").  ``--img-size`` sets
-cfg.img_size: N for N x N, HxW (height first, e.g. 512x640) or ``native`` for every frame
-at its own size; ``--ema-decay`` sets cfg.ema_decay (e.g. 0.999: train with a moving average
+[--img-size N | HxW | native] [--load-size N | HxW | native] [--ema-decay D]`` -- the reference's script
+entry point (ir:1730-1756) with cfg.mode taken from the command line (default: Config's "test").
+``--img-size`` sets cfg.img_size: N for N x N, HxW (height first, e.g. 512x640) or ``native`` for
+every frame at its own size; ``--load-size`` sets cfg.load_size, the training crop jitter: every
+training pair is resized to N x N, HxW or (``native``) left at its own size, and a random
+cfg.img_size window of it is the sample (e.g. ``--load-size 286`` with the default 256; validation
+and test ignore it); ``--ema-decay`` sets cfg.ema_decay (e.g. 0.999: train with a moving average
 of the generator weights).  Without a flag Config's value stands."""
 import argparse
 import sys
 
-from .data import parse_img_size
+from .data import parse_img_size, parse_load_size
 from .ir_colorization import Config, main
 
 
@@ -15,6 +18,7 @@ def config_from_argv(argv):
     ap = argparse.ArgumentParser(prog="python -m infrared-colorization-with-resnet-generator-and-patchgan_amd")
     ap.add_argument("mode", nargs="?", help="train or test (default: Config.mode)")
     ap.add_argument("--img-size", type=parse_img_size, default=argparse.SUPPRESS, metavar="N|HxW|native")
+    ap.add_argument("--load-size", type=parse_load_size, default=argparse.SUPPRESS, metavar="N|HxW|native")
     ap.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, metavar="D")
     a = ap.parse_args(argv)
     cfg = Config()
@@ -22,6 +26,8 @@ def config_from_argv(argv):
         cfg.mode = a.mode
     if hasattr(a, "img_size"):
         cfg.img_size = a.img_size
+    if hasattr(a, "load_size"):
+        cfg.load_size = a.load_size
     if hasattr(a, "ema_decay"):
         cfg.ema_decay = a.ema_decay
     return cfg

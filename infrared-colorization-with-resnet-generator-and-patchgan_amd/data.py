@@ -23,6 +23,17 @@ img_size=None, ir:817, 847).  A rectangular target follows cv::resize's own disp
 per call (copy / area tables per axis / the linear path when either axis upscales);
 at the source size the device path is one ``irgan_u8_native_to_unit`` launch.
 
+``load_size`` (read in one place, ``load_hw``: an int, a (height, width) pair, "native", or
+None = off, the default) adds the pix2pix crop jitter to TRAINING samples (augment=True): the
+image is resized to the load size, a random ``img_size`` window -- the same (oy, ox) for IR and
+RGB, drawn with python ``random`` after the flip draw -- is cut out of it, and flip and float
+conversion see that window (the IR max rule of ir:1142 included).  "native" cuts the window
+out of the decoded frame.  ``__getitem__`` does that on the host; ``raw`` only draws, and the
+``irgan_*_crop_*`` entries compute the window alone on the device, bit for bit the host's.
+augment=False (validation, the val split of train_kaist, run_test) ignores ``load_size`` and
+resizes straight to ``img_size``; with "native" the validation scale therefore differs from
+the training crops'.  With ``load_size=None`` no extra draw is made and nothing changes.
+
 Decoding: OpenCV is not available in this image, so files are decoded with PIL
 and converted with cv2's rules (IMREAD_GRAYSCALE: 16-bit PNG -> high byte,
 colour -> BGR2GRAY fixed-point weights; IMREAD_COLOR + BGR2RGB).  INTER_AREA is
@@ -44,7 +55,7 @@ import torch
 from . import _lib
 from .ops import P, stream
 
-__all__ = ["EXTS", "target_hw", "parse_img_size", "area_table", "linear_area_table", "resize_area_u8", "resize_linear_area_u8", "imread_gray", "imread_rgb", "load_ir_image", "load_rgb_image",
+__all__ = ["EXTS", "target_hw", "parse_img_size", "load_hw", "parse_load_size", "area_table", "linear_area_table", "resize_area_u8", "resize_linear_area_u8", "imread_gray", "imread_rgb", "load_ir_image", "load_rgb_image",
            "collect_kaist_ir_files_from_sets", "scan_kaist_pairs", "KAISTPairDataset", "DeviceResizer",
            "collate_raw", "kaist_loader"]
 
@@ -220,6 +231,81 @@ def parse_img_size(text: str):
     return size
 
 
+def load_hw(load_size, src_hw=None):
+    """The one reading of ``load_size`` (Config, KAISTPairDataset, DeviceResizer), the size a
+    training image is resized to before a random ``img_size`` window is cut out of it -> the
+    (height, width) of that load-size image for a source of size ``src_hw``:
+
+    * an int S or a (height, width) pair: target_hw's forms, height first;
+    * the string "native": ``src_hw`` itself, nothing is resampled and the window is cut out
+      of the decoded frame; with no source given (src_hw None) that is an error.
+
+    None (the option is off) is not a size: callers test for it first.  Anything else raises
+    ValueError."""
+    if isinstance(load_size, str):
+        if load_size.strip().lower() != "native":
+            raise ValueError(f"load_size must be a positive int, a (height, width) pair of them or 'native', "
+                             f"got {load_size!r}")
+        if src_hw is None:
+            raise ValueError("load_size='native' keeps the source size, and there is no source here")
+        return int(src_hw[0]), int(src_hw[1])
+    if load_size is None:
+        raise ValueError("load_size=None turns the crop off; there is no load size to read")
+    try:
+        return target_hw(load_size)
+    except ValueError:
+        raise ValueError(f"load_size must be a positive int, a (height, width) pair of them or 'native', "
+                         f"got {load_size!r}") from None
+
+
+def parse_load_size(text: str):
+    """The command line's ``--load-size N | HxW | native`` as a ``load_size`` value."""
+    t = text.strip().lower()
+    if t == "native":
+        return "native"
+    try:
+        parts = [int(p) for p in t.split("x")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2):
+        raise ValueError(f"--load-size takes N, HxW (height first) or 'native', got {text!r}")
+    size = parts[0] if len(parts) == 1 else tuple(parts)
+    load_hw(size)
+    return size
+
+
+def _check_crop(img_size, load_size):
+    """``load_size`` against ``img_size`` as far as it can be judged without a source: a
+    malformed value, a crop with no size (img_size None) and an int / pair load size below
+    the crop on either axis raise ValueError ('native' is judged per batch, _window)."""
+    if load_size is None:
+        return
+    if img_size is None:
+        load_hw(load_size, (1, 1))
+        raise ValueError("load_size crops a window of img_size out of the load-size image: it needs an img_size, "
+                         "not None")
+    h, w = target_hw(img_size)
+    lh, lw = load_hw(load_size, (h, w))
+    if lh < h or lw < w:
+        raise ValueError(f"load_size {lh}x{lw} is smaller than img_size {h}x{w}: the crop does not fit")
+
+
+def _window(img_size, load_size, ir_hw, rgb_hw):
+    """((Hl, Wl), (h, w)): the load-size image the IR and RGB sources of sizes ``ir_hw`` /
+    ``rgb_hw`` are brought to, and the window cut out of it.  'native' sources that differ
+    from each other or are smaller than the window raise RuntimeError."""
+    h, w = target_hw(img_size)
+    L, Lr = load_hw(load_size, ir_hw), load_hw(load_size, rgb_hw)
+    if L != Lr:
+        raise RuntimeError(f"load_size='native' crops each frame at its own size, but the IR frames are "
+                           f"{L[0]}x{L[1]} and the RGB frames {Lr[0]}x{Lr[1]}: one window cannot serve both -- "
+                           "give a load_size")
+    if L[0] < h or L[1] < w:
+        raise RuntimeError(f"load_size='native': the frames are {L[0]}x{L[1]}, smaller than the "
+                           f"{h}x{w} crop (img_size)")
+    return L, (h, w)
+
+
 def resize_area_u8(img: np.ndarray, size) -> np.ndarray:
     """cv2.resize(img, (w, h), interpolation=INTER_AREA) for uint8 HxW or HxWxC input,
     host side, with (h, w) = target_hw(size, img.shape[:2]) -- note the order: ``size``
@@ -363,12 +449,16 @@ def scan_kaist_pairs(roots):
 class KAISTPairDataset(torch.utils.data.Dataset):
     """ir:1045-1177 with the reference's signature and item contract; see the
     module docstring for the device path (``raw`` + ``kaist_loader``).  ``img_size``:
-    target_hw's forms -- an int, (height, width), or None for each pair's own size."""
+    target_hw's forms -- an int, (height, width), or None for each pair's own size.
+    ``load_size`` (load_hw's forms; None, the default: off) is the paired random-crop jitter
+    of a training dataset: each image is resized to the load size and a random ``img_size``
+    window of it, the same for IR and RGB, is the sample; augment=False ignores it."""
 
-    def __init__(self, root, img_size=256, augment=True, indices=None, verbose=True):
+    def __init__(self, root, img_size=256, augment=True, indices=None, verbose=True, load_size=None):
         super().__init__()
         target_hw(img_size, (1, 1))   # reject a malformed size here, not in a worker
-        self.img_size, self.augment = img_size, augment
+        _check_crop(img_size, load_size)
+        self.img_size, self.augment, self.load_size = img_size, augment, load_size
         all_ir, all_rgb = scan_kaist_pairs(root)
         if indices is not None:
             self.ir_paths = [all_ir[i] for i in indices]
@@ -384,11 +474,29 @@ class KAISTPairDataset(torch.utils.data.Dataset):
     def _flip(self):
         return bool(self.augment and random.random() < 0.5)   # ir:1166, python RNG in the worker
 
+    def _crop(self, ir_hw, rgb_hw):
+        """The crop draw of a training sample with a load_size: ((Hl, Wl), (h, w), (oy, ox)),
+        python RNG in the worker, after the flip draw; None (and no draw) otherwise."""
+        if not self.augment or self.load_size is None:
+            return None
+        L, (h, w) = _window(self.img_size, self.load_size, ir_hw, rgb_hw)
+        oy = random.randint(0, L[0] - h)
+        ox = random.randint(0, L[1] - w)
+        return L, (h, w), (oy, ox)
+
     def __getitem__(self, idx):
-        ir = _unit_ir(resize_area_u8(imread_gray(self.ir_paths[idx]), self.img_size))
-        rgb = np.clip(resize_area_u8(imread_rgb(self.rgb_paths[idx]), self.img_size).astype(np.float32) / 255.0,
-                      0.0, 1.0)
-        if self._flip():
+        ir8, rgb8 = imread_gray(self.ir_paths[idx]), imread_rgb(self.rgb_paths[idx])
+        flip = self._flip()
+        crop = self._crop(ir8.shape[:2], rgb8.shape[:2])
+        if crop is None:
+            ir8, rgb8 = resize_area_u8(ir8, self.img_size), resize_area_u8(rgb8, self.img_size)
+        else:   # resize to the load size, keep the window; the IR max rule sees the window
+            L, (h, w), (oy, ox) = crop
+            ir8 = resize_area_u8(ir8, L)[oy:oy + h, ox:ox + w]
+            rgb8 = resize_area_u8(rgb8, L)[oy:oy + h, ox:ox + w]
+        ir = _unit_ir(ir8)
+        rgb = np.clip(rgb8.astype(np.float32) / 255.0, 0.0, 1.0)
+        if flip:
             ir = np.fliplr(ir).copy()
             rgb = np.fliplr(rgb).copy()
         ir_t = torch.from_numpy(ir).unsqueeze(0)
@@ -396,11 +504,15 @@ class KAISTPairDataset(torch.utils.data.Dataset):
         return {"ir": ir_t * 2.0 - 1.0, "rgb": rgb_t * 2.0 - 1.0}
 
     def raw(self, idx):
-        """Decoded full-resolution uint8 images and the flip draw: the host half of
-        the device path (resize / flip / normalisation run in csrc/data.hip)."""
-        return {"ir_u8": torch.from_numpy(imread_gray(self.ir_paths[idx])),
-                "rgb_u8": torch.from_numpy(imread_rgb(self.rgb_paths[idx])),
-                "flip": int(self._flip())}
+        """Decoded full-resolution uint8 images, the flip draw and, for a training sample
+        with a load_size, the crop draw ``"crop": (oy, ox)``: the host half of the device
+        path (resize / crop / flip / normalisation run in csrc/data.hip)."""
+        ir8, rgb8 = imread_gray(self.ir_paths[idx]), imread_rgb(self.rgb_paths[idx])
+        item = {"ir_u8": torch.from_numpy(ir8), "rgb_u8": torch.from_numpy(rgb8), "flip": int(self._flip())}
+        crop = self._crop(ir8.shape[:2], rgb8.shape[:2])
+        if crop is not None:
+            item["crop"] = crop[2]
+        return item
 
 
 class _RawView(torch.utils.data.Dataset):
@@ -419,14 +531,19 @@ class _RawView(torch.utils.data.Dataset):
 def collate_raw(items):
     """Stack decoded items into uint8 batches (pinned by the DataLoader).  Each modality
     needs one source size within the batch (one resize launch per modality); the IR and
-    RGB sources may differ (the reference resizes each image on its own, ir:1139, 1156)."""
+    RGB sources may differ (the reference resizes each image on its own, ir:1139, 1156).
+    Items that carry a crop draw (KAISTPairDataset.raw with a load_size) add ``"crop"``, the
+    draws as an int32 (B, 2) tensor of (oy, ox); without them the key is absent."""
     for key in ("ir_u8", "rgb_u8"):
         shapes = {tuple(it[key].shape[:2]) for it in items}
         if len(shapes) != 1:
             raise RuntimeError(f"a device batch needs one {key[:-3]} source size, got {sorted(shapes)}")
-    return {"ir_u8": torch.stack([it["ir_u8"] for it in items]),
-            "rgb_u8": torch.stack([it["rgb_u8"] for it in items]),
-            "flip": torch.tensor([it["flip"] for it in items], dtype=torch.uint8)}
+    batch = {"ir_u8": torch.stack([it["ir_u8"] for it in items]),
+             "rgb_u8": torch.stack([it["rgb_u8"] for it in items]),
+             "flip": torch.tensor([it["flip"] for it in items], dtype=torch.uint8)}
+    if any("crop" in it for it in items):
+        batch["crop"] = torch.tensor([it["crop"] for it in items], dtype=torch.int32).reshape(len(items), 2)
+    return batch
 
 
 class DeviceResizer:
@@ -434,11 +551,18 @@ class DeviceResizer:
     the device, (h, w) = target_hw(img_size, source size): per modality one
     area-resize+flip launch and one normalisation launch (the IR max rule of ir:1142
     included), or, where the target is the source size, the single native pass
-    (irgan_u8_native_to_unit).  Tables cached per (source n, target n)."""
+    (irgan_u8_native_to_unit).  Tables cached per (source n, target n).
 
-    def __init__(self, img_size, device):
+    ``load_size`` (load_hw's forms; None: off): a batch that carries ``"crop"`` (collate_raw:
+    the training samples of a dataset with a load_size) is resized to the load size and only
+    its (h, w) window at each image's (oy, ox) is computed -- the same dispatch, applied to
+    source -> load size, through the *_crop entries; tables per (source n, load n).  A batch
+    without ``"crop"`` (validation) goes straight to img_size as above."""
+
+    def __init__(self, img_size, device, load_size=None):
         target_hw(img_size, (1, 1))
-        self.img_size, self.device = img_size, torch.device(device)
+        _check_crop(img_size, load_size)
+        self.img_size, self.load_size, self.device = img_size, load_size, torch.device(device)
         self._tabs = {}
 
     def _tab(self, n, d):
@@ -455,51 +579,79 @@ class DeviceResizer:
             t = self._tabs[key] = (torch.from_numpy(ofs).to(self.device), torch.from_numpy(coef).to(self.device), lim)
         return t
 
-    def resize_u8(self, u8, C, flip=None, img_max=None, hw=None):
+    def resize_u8(self, u8, C, flip=None, img_max=None, hw=None, crop=None, load=None):
         """(B,H,W[,C]) uint8 device batch -> (B,C,h,w) uint8 (cv2.resize INTER_AREA,
         optional per-image horizontal flip).  ``hw`` overrides the resizer's own target
-        (run_test: the ground truth goes to its prediction's size)."""
+        (run_test: the ground truth goes to its prediction's size).  ``crop`` (int32 (B, 2)
+        device tensor of (oy, ox), with ``load`` = (Hl, Wl)): the resize goes to ``load`` and
+        the result is its (h, w) window at each image's offset."""
         if u8.dtype != torch.uint8 or not u8.is_cuda:
             raise ValueError("resize_u8 takes a uint8 device tensor")
         u8 = u8.contiguous()
         B, H, W = u8.shape[:3]
         h, w = hw if hw is not None else target_hw(self.img_size, (H, W))
+        Hl, Wl = load if crop is not None else (h, w)   # the size the tables resize to
+        win = () if crop is None else (P(crop), h, w)
         out8 = torch.empty(B, C, h, w, dtype=torch.uint8, device=self.device)
-        if H < h or W < w:   # an upscaling axis: OpenCV's linear path with area coefficients
-            yo, yc, _ = self._ltab(H, h, False)
-            xo, xc, xlim = self._ltab(W, w, True)
-            _lib.call("irgan_linear_area_resize_u8", P(u8), B, H, W, C, ctypes.c_int64(H * W * C), P(yo), P(yc), h,
-                      P(xo), P(xc), xlim, w, P(flip) if flip is not None else None, P(out8),
+        if H < Hl or W < Wl:   # an upscaling axis: OpenCV's linear path with area coefficients
+            yo, yc, _ = self._ltab(H, Hl, False)
+            xo, xc, xlim = self._ltab(W, Wl, True)
+            _lib.call("irgan_linear_area_resize_u8" if crop is None else "irgan_linear_area_resize_crop_u8", P(u8), B,
+                      H, W, C, ctypes.c_int64(H * W * C), P(yo), P(yc), Hl, P(xo), P(xc), xlim, Wl, *win,
+                      P(flip) if flip is not None else None, P(out8),
                       P(img_max) if img_max is not None else None, stream())
             return out8
-        yp, ys, yw = self._tab(H, h)   # (an axis that keeps its size: the identity table, unit weights)
-        xp, xs, xw = self._tab(W, w)
-        _lib.call("irgan_area_resize_u8", P(u8), B, H, W, C, ctypes.c_int64(H * W * C), P(yp), P(ys), P(yw), h,
-                  P(xp), P(xs), P(xw), w, P(flip) if flip is not None else None, P(out8),
+        yp, ys, yw = self._tab(H, Hl)   # (an axis that keeps its size: the identity table, unit weights)
+        xp, xs, xw = self._tab(W, Wl)
+        _lib.call("irgan_area_resize_u8" if crop is None else "irgan_area_resize_crop_u8", P(u8), B, H, W, C,
+                  ctypes.c_int64(H * W * C), P(yp), P(ys), P(yw), Hl, P(xp), P(xs), P(xw), Wl, *win,
+                  P(flip) if flip is not None else None, P(out8),
                   P(img_max) if img_max is not None else None, stream())
         return out8
 
-    def _one(self, u8, C, flip, max_rule, keep_u8=False):
+    def _one(self, u8, C, flip, max_rule, keep_u8=False, crop=None, load=None):
         """(B,C,h,w) float32 [-1, 1]; keep_u8: also the resized uint8 batch (what the
-        reference's loaders hold before their float conversion)."""
+        reference's loaders hold before their float conversion).  ``crop`` / ``load``: as
+        resize_u8 (the resized batch is then the window)."""
         B, H, W = u8.shape[:3]
         h, w = target_hw(self.img_size, (H, W))
+        Hl, Wl = load if crop is not None else (h, w)
         mx = torch.zeros(B, dtype=torch.int32, device=self.device)
         out = torch.empty(B, C, h, w, dtype=torch.float32, device=self.device)
-        if (h, w) == (H, W):   # nothing to resize: uint8 NHWC -> float NCHW in one pass
+        if (Hl, Wl) == (H, W):   # nothing to resize: uint8 NHWC -> float NCHW in one pass
             if u8.dtype != torch.uint8 or not u8.is_cuda:
                 raise ValueError("the device path takes a uint8 device tensor")
             u8 = u8.contiguous()
             out8 = torch.empty(B, C, h, w, dtype=torch.uint8, device=self.device) if keep_u8 else None
-            _lib.call("irgan_u8_native_to_unit", P(u8), B, H, W, C, ctypes.c_int64(H * W * C),
-                      P(flip) if flip is not None else None, int(max_rule), P(mx), P(out),
-                      P(out8) if keep_u8 else None, stream())
+            win = () if crop is None else (P(crop), h, w)
+            _lib.call("irgan_u8_native_to_unit" if crop is None else "irgan_u8_native_crop_to_unit", P(u8), B, H, W, C,
+                      ctypes.c_int64(H * W * C), *win, P(flip) if flip is not None else None, int(max_rule), P(mx),
+                      P(out), P(out8) if keep_u8 else None, stream())
             return (out, out8) if keep_u8 else out
-        out8 = self.resize_u8(u8, C, flip, mx)
+        out8 = self.resize_u8(u8, C, flip, mx, crop=crop, load=load)
         _lib.call("irgan_u8_to_unit", P(out8), B, ctypes.c_int64(C * h * w), P(mx), int(max_rule), P(out), stream())
         return (out, out8) if keep_u8 else out
 
+    def _crop_of(self, batch):
+        """The batch's crop draws, checked on the host: ((Hl, Wl), int32 (B, 2) CPU tensor),
+        or (None, None) for a batch without them.  Nothing has touched the device yet."""
+        if "crop" not in batch:
+            return None, None
+        if self.load_size is None:
+            raise ValueError("this batch carries crop offsets, but the resizer has no load_size to crop from")
+        L, (h, w) = _window(self.img_size, self.load_size, batch["ir_u8"].shape[1:3], batch["rgb_u8"].shape[1:3])
+        crop = torch.as_tensor(batch["crop"]).to("cpu", torch.int32)
+        B = batch["ir_u8"].shape[0]
+        if tuple(crop.shape) != (B, 2):
+            raise ValueError(f"crop must hold one (oy, ox) per image, shape ({B}, 2), got {tuple(crop.shape)}")
+        oy, ox = crop[:, 0], crop[:, 1]
+        if int(oy.min()) < 0 or int(oy.max()) > L[0] - h or int(ox.min()) < 0 or int(ox.max()) > L[1] - w:
+            raise ValueError(f"crop offsets {crop.tolist()} leave the {L[0]}x{L[1]} load-size image: a {h}x{w} window "
+                             f"needs 0 <= oy <= {L[0] - h}, 0 <= ox <= {L[1] - w}")
+        return L, crop.contiguous()
+
     def __call__(self, batch):
+        load, crop = self._crop_of(batch)
         hw_ir = target_hw(self.img_size, batch["ir_u8"].shape[1:3])
         hw_rgb = target_hw(self.img_size, batch["rgb_u8"].shape[1:3])
         if hw_ir != hw_rgb:
@@ -509,7 +661,10 @@ class DeviceResizer:
         ir8 = batch["ir_u8"].to(self.device, non_blocking=True).contiguous()
         rgb8 = batch["rgb_u8"].to(self.device, non_blocking=True).contiguous()
         flip = batch["flip"].to(self.device, non_blocking=True)
-        return {"ir": self._one(ir8, 1, flip, True), "rgb": self._one(rgb8, 3, flip, False)}
+        if crop is not None:
+            crop = crop.to(self.device, non_blocking=True)
+        return {"ir": self._one(ir8, 1, flip, True, crop=crop, load=load),
+                "rgb": self._one(rgb8, 3, flip, False, crop=crop, load=load)}
 
 
 class _DeviceLoader:
@@ -528,9 +683,11 @@ def kaist_loader(dataset: KAISTPairDataset, batch_size, device, shuffle=False, d
                  sampler=None):
     """DataLoader over ``dataset.raw`` (workers decode only) whose batches are
     resized / flipped / normalised on ``device`` (DeviceResizer) to ``dataset.img_size``
-    (target_hw's forms; None: the batch's own size, one size per batch by collate_raw)."""
+    (target_hw's forms; None: the batch's own size, one size per batch by collate_raw).
+    A training dataset's ``load_size`` comes along: its batches carry the crop draws and the
+    device computes only the window (augment=False draws none and resizes as above)."""
     base = dataset.dataset if isinstance(dataset, torch.utils.data.Subset) else dataset
     dl = torch.utils.data.DataLoader(_RawView(dataset), batch_size=batch_size, shuffle=shuffle and sampler is None,
                                      sampler=sampler, num_workers=num_workers, collate_fn=collate_raw,
                                      pin_memory=torch.device(device).type == "cuda", drop_last=drop_last)
-    return _DeviceLoader(dl, DeviceResizer(base.img_size, device))
+    return _DeviceLoader(dl, DeviceResizer(base.img_size, device, load_size=base.load_size))

@@ -106,6 +106,9 @@ class Config:
                                          # ranks (nn.SyncBatchNorm semantics) in the fused step; off -> refused
         self.ema_decay = 0.0             # in (0, 1): keep an exponential moving average of G's weights (updated
                                          # in G's Adam pass); train_kaist validates and saves it as netG_ema_*.pth
+        self.load_size = None            # S, (height, width) or "native" (data.load_hw): train_kaist resizes each
+                                         # training pair to this size and trains on a random img_size crop of it
+                                         # (validation and run_test go straight to img_size); None = off
 
 
 # =============================================================================
@@ -918,7 +921,9 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
     """ir:1549-1723 with the fused HIP step.  ``dataset=None`` trains on the KAIST
     pairs under ``cfg.train_roots`` (data.KAISTPairDataset: decode on the host,
     INTER_AREA resize to ``cfg.img_size`` -- S, (height, width) or None for the frames'
-    own size -- + paired flip + normalisation on the device); any dataset
+    own size -- + paired flip + normalisation on the device; with ``cfg.load_size`` the
+    training pairs are resized to that size and a random ``cfg.img_size`` crop is taken,
+    the validation split is not); any dataset
     yielding {'ir','rgb'} (e.g. SyntheticPairDataset) may be passed instead.
     ``trainer_hook(trainer)`` (optional) runs once after the networks are built
     (e.g. to load D / VGG weights from files)."""
@@ -939,7 +944,7 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
     random.shuffle(idxs)
     if dataset is None:
         train_ds = KAISTPairDataset(cfg.train_roots, img_size=cfg.img_size, augment=True, indices=idxs[:train_size],
-                                    verbose=rank == 0)
+                                    verbose=rank == 0, load_size=getattr(cfg, "load_size", None))
         val_ds = KAISTPairDataset(cfg.train_roots, img_size=cfg.img_size, augment=False,
                                   indices=idxs[train_size:][rank::world], verbose=rank == 0)
         sampler = None
