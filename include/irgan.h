@@ -171,6 +171,22 @@ IRGAN_API int irgan_conv_wgrad(const irgan_conv_desc* d, const void* x, const vo
 IRGAN_API int irgan_conv_wgrad_ws(const irgan_conv_desc* d, const void* x, const void* dy, float* dw,
                         int32_t splitk, float* ws, int64_t ws_floats, irgan_stream_t s);
 
+/* count (1..4) weight gradients of ONE geometry d in one launch and one ordered reduce:
+ * dw[i] += the weight gradient of (x[i], dy[i]), i < count (host arrays of device pointers).
+ * For weight gradients nothing waits for, e.g. the ResnetBlock convs of a backward (ir:386-411):
+ * the problems share the CUs, so each is split 1 / count as many ways and 1 / count of the
+ * split-K partial bytes per layer are written and read back.  bf16, 3x3, stride 1, Cin % 128 ==
+ * 0, Cout % 128 == 0, ld / off % 8 == 0, operand bytes < 2^31, and ws must hold count * splits *
+ * (Cout*9*Cin) floats (splits <= CUs / (count * tiles)); otherwise, or with count outside 1..4,
+ * IRGAN_EUNSUPPORTED and nothing launched (the caller runs irgan_conv_wgrad_ws per layer).
+ * Never atomics: bit-reproducible run to run with or without IRGAN_CONV_DETERMINISTIC; count == 1
+ * gives irgan_conv_wgrad_ws's bits.  With IRGAN_CONV_DETERMINISTIC every problem keeps the splits
+ * of a launch of its own (ws: count times that), so dw[i] is irgan_conv_wgrad_ws's bit for bit at
+ * any count: a deterministic step does not depend on the group size.  NULL pointers: IRGAN_EINVAL. */
+IRGAN_API int irgan_conv_wgrad_group(const irgan_conv_desc* d, int32_t count, const void* const* x,
+                           const void* const* dy, float* const* dw, float* ws, int64_t ws_floats,
+                           irgan_stream_t s);
+
 /* Weight re-pack: dst rows [R][Kp] (dtype) from the fp32 KRSC master
  * src[Cout][KH][KW][Cin], Kp = roundup(taps*Cp, kalign), taps and channels
  * zero-padded (Cp = max(cpad, channels)).  transpose=0: R = Cout, row =

@@ -30,6 +30,9 @@ extern "C" int irgan_conv_wgrad_rowspan(const irgan_conv_desc* d, const void* x,
                                         long ws_cap, hipStream_t st);
 extern "C" int irgan_conv_wgrad_pc(const irgan_conv_desc* d, const void* x, const void* dy, float* dw, int splitk,
                                    float* ws, long ws_cap, hipStream_t st);
+extern "C" int irgan_conv_wgrad_group_pc(const irgan_conv_desc* d, int count, const void* const* x,
+                                         const void* const* dy, float* const* dw, float* ws, long ws_cap,
+                                         hipStream_t st);
 extern "C" int irgan_conv_wgrad_narrow(const irgan_conv_desc* d, const void* x, const void* dy, float* dw, float* ws,
                                        long ws_cap, hipStream_t st);
 extern "C" int irgan_conv_wgrad_glds(const irgan_conv_desc* d, const void* x, const void* dy, float* dw, int splitk,
@@ -693,6 +696,17 @@ extern "C" int irgan_conv_wgrad_ws(const irgan_conv_desc* d, const void* x, cons
         return launch_wgrad<bf16_t>(d, x, dy, dw, splitk, st, ws, ws_floats);
     if (d->dtype == IRGAN_F32) return launch_wgrad<float>(d, x, dy, dw, splitk, st);
     return IRGAN_EUNSUPPORTED;
+}
+
+extern "C" int irgan_conv_wgrad_group(const irgan_conv_desc* d, int32_t count, const void* const* x,
+                                      const void* const* dy, float* const* dw, float* ws, int64_t ws_floats,
+                                      irgan_stream_t s) {
+    if (!d || !x || !dy || !dw) return IRGAN_EINVAL;
+    if (count < 1 || count > 4) return IRGAN_EUNSUPPORTED;
+    for (int i = 0; i < count; ++i)
+        if (!x[i] || !dy[i] || !dw[i]) return IRGAN_EINVAL;
+    // the wide-n producer/consumer kernel is the one grouped form (conv_wgrad_pc.hip)
+    return irgan_conv_wgrad_group_pc(d, count, x, dy, dw, ws, ws_floats, (hipStream_t)s);
 }
 
 extern "C" int irgan_weight_pack(const float* src, void* dst, int32_t dtype, int32_t Cout, int32_t KH, int32_t KW,

@@ -374,18 +374,56 @@ constexpr int W2_STAGES = 4;                 // 136 KiB
 #define W2_EXP 0
 #endif
 
-__global__ __launch_bounds__(W2_NT, 1) void wgrad_w2_kernel(const irgan_conv_desc d, const bf16_t* __restrict__ x,
-                                                            const bf16_t* __restrict__ dy, float* __restrict__ dw,
+//
+// Grouped launches (irgan_conv_wgrad_group): up to W2_GROUP_MAX problems of ONE geometry d share
+// a launch -- the weight gradients of several ResnetBlock convs, which nothing in the backward
+// waits for.  Tile index -> (problem, split, cot, cic, ty); a block reads its problem's x / dy
+// and writes that problem's region of the slab ([problem][split][n]).  With `count` problems the
+// CUs are shared by tiles * count tiles, so each takes 1 / count of the splits: 1 / count of the
+// slab bytes per layer, written and reduced, and the pipeline fill, the prologue barrier and the
+// store burst once per `count` layers' worth of segments.
+constexpr int W2_GROUP_MAX = 4;
+struct W2Prob {
+    const bf16_t* x;
+    const bf16_t* dy;
+    float* out;  // the problem's slab region (splits x n floats), or dw itself (atomics: no slab)
+};
+struct W2Group {
+    W2Prob p[W2_GROUP_MAX];
+};
+struct W2Sum {   // one problem of the reduce: its slab region and the dw it is summed into
+    const float* slab;
+    float* dw;
+};
+struct W2Sums {
+    W2Sum p[W2_GROUP_MAX];
+};
+// entry i of a by-value table, i block-uniform: scalar selects, no indexed copy of the table
+template <typename G>
+IRGAN_HD auto w2_pick(const G& g, int i) {
+    auto e = g.p[0];
+#pragma unroll
+    for (int k = 1; k < W2_GROUP_MAX; ++k)
+        if (i == k) e = g.p[k];
+    return e;
+}
+
+__global__ __launch_bounds__(W2_NT, 1) void wgrad_w2_kernel(const irgan_conv_desc d, const W2Group grp,
                                                             int segs_per_block, int nseg, int ntco, int nci2, int swz,
-                                                            float* __restrict__ slab) {
+                                                            int sk, int to_slab) {
     constexpr int DYR = 256, MI = 4, NJ = 6;
     __shared__ __attribute__((aligned(1024))) char smem[W2_STAGES * W2_STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles = ntco * nci2 * d.KH;
     const int t = swz ? xcd_tile_any(blockIdx.x, gridDim.x) : blockIdx.x;
-    const int split = t / tiles;
-    int r = t - split * tiles;
+    const int prob = t / (tiles * sk);
+    const int tp = t - prob * (tiles * sk);
+    const int split = tp / tiles;
+    int r = tp - split * tiles;
+    const W2Prob pr = w2_pick(grp, prob);
+    const bf16_t* const x = pr.x;
+    const bf16_t* const dy = pr.dy;
     const int ty = r % d.KH;
     r /= d.KH;
     const int cic = r % nci2, cot = r / nci2;
@@ -529,7 +567,8 @@ __global__ __launch_bounds__(W2_NT, 1) void wgrad_w2_kernel(const irgan_conv_des
 
     // C[row = co][col = n]: co = co0 + (wm*4 + i)*16 + 4g + rr, n = jj*16 + (lane & 15)
     const int K = d.KH * 3 * d.Cin;
-    float* const dst = slab ? slab + (long)split * d.Cout * K : nullptr;
+    float* __restrict__ const dst = to_slab ? pr.out + (long)split * d.Cout * K : nullptr;
+    float* __restrict__ const dw = pr.out;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -555,6 +594,45 @@ __global__ __launch_bounds__(256) void wgrad_pc_reduce(const float* __restrict__
     }
 }
 
+// the same sum for every problem of a grouped launch (blockIdx.y): problem p's `splits` slabs
+// into its own dw, each in wgrad_pc_reduce's order
+__global__ __launch_bounds__(256) void wgrad_w2_reduce(const W2Sums grp, int splits, long n) {
+    const W2Sum pr = w2_pick(grp, (int)blockIdx.y);
+    const long n4 = n / 4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        slab_sum4(pr.slab, splits, n, pr.dw, i);
+    }
+}
+
+// Splits of the wide-n kernel when `count` problems share the launch: one block per CU over
+// tiles * count tiles, at least 4 segments per split, at most `fit` splits (> 0: what a workspace
+// holds).  Returns sk with no empty split; *spb = segments per block.
+int w2_splits(const irgan_conv_desc* d, int count, long fit, int* spb, int* nseg) {
+    const int tiles = d->Cout / 128 * (d->Cin / 128) * d->KH;
+    *nseg = d->N * d->Ho * irgan_cdiv(d->Wo, 64);
+    int sk = irgan_cu_count() / (tiles * count);
+    if (sk < 1) sk = 1;
+    const int maxs = irgan_cdiv(*nseg, 4);
+    if (sk > maxs) sk = maxs;
+    if (fit > 0 && sk > fit) sk = (int)fit;
+    *spb = irgan_cdiv(*nseg, sk);
+    return irgan_cdiv(*nseg, *spb);
+}
+
+void w2_launch(const irgan_conv_desc* d, int count, const W2Group& grp, int sk, int spb, int nseg, bool to_slab,
+               hipStream_t st) {
+    const int ntco = d->Cout / 128, nci2 = d->Cin / 128;
+    wgrad_w2_kernel<<<ntco * nci2 * d->KH * sk * count, W2_NT, 0, st>>>(*d, grp, spb, nseg, ntco, nci2,
+                                                                          irgan_xcd_swz(), sk, to_slab ? 1 : 0);
+}
+
+// the geometry the wide-n kernel takes, apart from the operand type
+bool w2_shape(const irgan_conv_desc* d) {
+    return d->KW == 3 && d->sx == 1 && d->sy == 1 && d->Cout % 128 == 0 && d->Cin % 128 == 0 && d->Cout > 0 &&
+           d->Cin > 0 && d->ldx % 8 == 0 && d->xoff % 8 == 0 && d->ldy % 8 == 0 && d->yoff % 8 == 0 &&
+           (long)d->N * d->H * d->W * d->ldx * 2 < (1L << 31) && (long)d->N * d->Ho * d->Wo * d->ldy * 2 < (1L << 31);
+}
+
 }  // namespace
 
 // Preconditions (else IRGAN_EUNSUPPORTED, nothing launched): bf16 operands, stride 1,
@@ -577,23 +655,15 @@ extern "C" int irgan_conv_wgrad_pc(const irgan_conv_desc* d, const void* x, cons
     const int cus = irgan_cu_count();
     const int swz = irgan_xcd_swz();
     if (w2) {
-        const int ntco = d->Cout / 128, nci2 = d->Cin / 128;
-        const int tiles = ntco * nci2 * d->KH;
-        const int nseg = d->N * d->Ho * irgan_cdiv(d->Wo, 64);
-        int sk = cus / tiles;
-        if (sk < 1) sk = 1;
-        const int maxs = irgan_cdiv(nseg, 4);
-        if (sk > maxs) sk = maxs;
         const long n = (long)d->Cout * d->KH * 3 * d->Cin;
-        if (irgan_det(d)) {
-            const long fit = ws ? ws_cap / n : 1;
-            if (sk > fit) sk = (int)(fit > 1 ? fit : 1);
-        }
-        const int spb = irgan_cdiv(nseg, sk);
-        sk = irgan_cdiv(nseg, spb);
+        long fit = 0;   // deterministic: at most the splits the workspace holds
+        if (irgan_det(d)) fit = ws && ws_cap / n > 1 ? ws_cap / n : 1;
+        int spb, nseg;
+        const int sk = w2_splits(d, 1, fit, &spb, &nseg);
         float* slab = (!(W2_EXP & 8) && ws && sk > 1 && (long)sk * n <= ws_cap) ? ws : nullptr;
-        wgrad_w2_kernel<<<tiles * sk, W2_NT, 0, st>>>(*d, (const bf16_t*)x, (const bf16_t*)dy, dw, spb, nseg, ntco,
-                                                      nci2, swz, slab);
+        W2Group grp = {};
+        grp.p[0] = {(const bf16_t*)x, (const bf16_t*)dy, slab ? slab : dw};
+        w2_launch(d, 1, grp, sk, spb, nseg, slab != nullptr, st);
         if (slab) {
             const int blocks = (int)std::min<long>(irgan_cdiv(n / 4, 256), 2048);
             wgrad_pc_reduce<<<blocks, 256, 0, st>>>(slab, sk, n, dw);
@@ -635,6 +705,37 @@ extern "C" int irgan_conv_wgrad_pc(const irgan_conv_desc* d, const void* x, cons
     } else if (splitk == 1) {
         // (atomics with one split: still correct, dw accumulates)
     }
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// `count` (1 .. W2_GROUP_MAX) weight gradients of one geometry in one wide-n launch and one
+// reduce (irgan_conv_wgrad_group).  Always through the slab, never atomics: ws must hold
+// count * sk * n floats, laid out [problem][split][n].  count == 1 is irgan_conv_wgrad_pc's
+// partition and arithmetic.  Else IRGAN_EUNSUPPORTED, nothing launched.
+// IRGAN_CONV_DETERMINISTIC: every problem keeps the splits it has in a launch of its own
+// (count x 252 blocks at the resblock shape), so dw[i] is irgan_conv_wgrad_pc's bit for bit
+// whatever the count -- the deterministic step does not depend on the group size.
+extern "C" int irgan_conv_wgrad_group_pc(const irgan_conv_desc* d, int count, const void* const* x,
+                                         const void* const* dy, float* const* dw, float* ws, long ws_cap,
+                                         hipStream_t st) {
+    if (count < 1 || count > W2_GROUP_MAX || d->dtype != IRGAN_BF16 || d->KH != 3 || !w2_shape(d))
+        return IRGAN_EUNSUPPORTED;
+    if ((long)d->N * d->Ho * d->Wo <= 0) return 0;
+    const long n = (long)d->Cout * 9 * d->Cin;
+    int spb, nseg;
+    const int sk = w2_splits(d, irgan_det(d) ? 1 : count, 0, &spb, &nseg);
+    if (!ws || (long)count * sk * n > ws_cap) return IRGAN_EUNSUPPORTED;
+    W2Group grp = {};
+    W2Sums sums = {};
+    for (int i = 0; i < count; ++i) {
+        float* const slab = ws + (long)i * sk * n;
+        grp.p[i] = {(const bf16_t*)x[i], (const bf16_t*)dy[i], slab};
+        sums.p[i] = {slab, dw[i]};
+    }
+    w2_launch(d, count, grp, sk, spb, nseg, true, st);
+    const int blocks = (int)std::min<long>(irgan_cdiv(n / 4, 256), 2048);
+    wgrad_w2_reduce<<<dim3(blocks, count), 256, 0, st>>>(sums, sk, n);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -758,10 +758,14 @@ class GenConv:
         """z = conv(x), y = resample(act(norm(z))) (INLayer.resample_fwd)."""
         self.norm.resample_fwd(g, self.name, self.pc, x, z, a_name, act, y, fused, plain, conv8=self._conv8(st))
 
-    def bwd(self, g: Buffers, st, dy: Feat, z: Feat, act, dz: Feat, x: Feat, dx: Feat, accumulate=False, padbuf=None):
+    def bwd(self, g: Buffers, st, dy: Feat, z: Feat, act, dz: Feat, x: Feat, dx: Feat, accumulate=False, padbuf=None,
+            pend: list = None):
         """Backward of fwd(): dz = the norm's backward of dy (in place when dz is dy), the weight
         gradient from x and dz, dx (+)= backward-data of dz.  The bf16 ResnetBlock convs launch
-        the backward-data first, every other case the weight gradient."""
+        the backward-data first, every other case the weight gradient.  ``pend`` (the ResnetBlock
+        convs off the e4m3 path): the weight gradient is not launched but appended to it as
+        (layer, x, dz) -- the caller launches several at once (wgrad_flush) and keeps x and dz
+        unchanged until then."""
         e, on = self.eng, st.on[self.group]
         dz8 = Feat(g.get(self.dy8, (*dz.t.shape[:3], dz.C), torch.float8_e4m3fn)) if on else None
         self.norm.bwd(g, self.name, dy, z, act, dz, db=e._bgrad(self.key + ".bias"),
@@ -782,7 +786,11 @@ class GenConv:
         else:
             ops.conv_dgrad(self.pc, dz, dx, accumulate=accumulate, pad_buf=padbuf)
         if self.group == "res":
-            self._wgrad(st, Feat(g.d[self.xp]) if self.xp else x, dz)
+            xw = Feat(g.d[self.xp]) if self.xp else x
+            if pend is None:
+                self._wgrad(st, xw, dz)
+            else:
+                pend.append((self, xw, dz))
 
     def _wgrad(self, st, x: Feat, dz: Feat, dz8: Feat = None):
         """The weight gradient: on the e4m3 copies (the operand with the scale it was made
@@ -794,6 +802,18 @@ class GenConv:
             if ops.conv_wgrad_fp8(self.pc.spec, x8, dz8, dqx, e.f8a.dqp(self.rec.s_dy), dw):
                 return
         ops.conv_wgrad(self.pc.spec, x, dz, dw, e.dtype)
+
+
+def wgrad_flush(eng, pend):
+    """Launch the deferred weight gradients ``pend`` (GenConv.bwd; one conv shape): as one grouped
+    launch where the library takes them (ops.conv_wgrad_group), else layer by layer."""
+    if not pend:
+        return
+    dws = [eng.store.krsc(c.key + ".weight", eng.store.grad) for c, _, _ in pend]
+    if not ops.conv_wgrad_group(pend[0][0].pc.spec, [x for _, x, _ in pend], [dz for _, _, dz in pend], dws,
+                                eng.dtype):
+        for (c, x, dz), dw in zip(pend, dws):
+            ops.conv_wgrad(c.pc.spec, x, dz, dw, eng.dtype)
 
 
 # ----------------------------------------------------------------------------
@@ -1148,18 +1168,42 @@ class GeneratorEngine:
             ops.upsample_bwd(dy1, dh)
         ready("up1_up.weight" if self.no_aa_up else "up1_conv.0.weight")
         # resblocks, reversed: dh holds d h_{b+1}; becomes d h_b in place
-        dt_ = Feat(g.get("dtmp", (B, H2, W2, c2), T))
+        # Off the e4m3 path their weight gradients -- which nothing in the backward reads -- are
+        # deferred and launched ``ngrp`` layers at a time (wgrad_flush).  Each deferred layer's dz
+        # then lands in its own slot of a ring of ngrp buffers, rewritten only after the flush that
+        # read it (same stream), and ready() follows the flush that made its tail final.
+        ngrp = 0 if st.on["res"] else ops.WGRAD_GROUP[0]
         dr = Feat(g.get("dtmp2", (B, H2, W2, c2), T))
+        if ngrp:
+            ring = [Feat(g.get(f"dz_ring{i}", (B, H2, W2, c2), T)) for i in range(ngrp)]
+            pend = []
+        else:
+            ring, pend = [Feat(g.get("dtmp", (B, H2, W2, c2), T)), dr], None   # rb's dz; ra's in place
+
+        def flush(full):
+            if pend and (full or len(pend) >= ngrp):
+                wgrad_flush(self, pend)
+                ready(f"{pend[-1][0].key}.weight")   # final from the last flushed layer to the end
+                pend.clear()
+
         drop = self.use_dropout and "dropout_seed" in g.state
         for b in reversed(range(self.n_blocks)):
             ra, rb = self.blocks[b]
+            k = 2 * (self.n_blocks - 1 - b)   # rb is the backward's k-th ResnetBlock conv, ra its k+1-th
             t = Feat(g.d[f"td{b}"] if drop else g.d[f"t{b}"])   # rb's input: the dropped-out t
-            rb.bwd(g, st, dh, Feat(g.d[f"r2_{b}"]), ACT_NONE, dt_, t, dr, padbuf=padbuf)
+            rb.bwd(g, st, dh, Feat(g.d[f"r2_{b}"]), ACT_NONE, ring[k % len(ring)], t, dr, padbuf=padbuf,
+                   pend=pend)
+            flush(False)
             if drop:   # backward of the dropout: the same mask and scale on the gradient
                 ops.dropout(dr, dr, g.state["dropout_seed"] + 2 * b)
-            ra.bwd(g, st, dr, Feat(g.d[f"r1_{b}"]), ACT_RELU, dr, Feat(g.d[f"h{b}"]), dh, accumulate=True,
-                   padbuf=padbuf)
-            ready(f"{ra.key}.weight")
+            ra.bwd(g, st, dr, Feat(g.d[f"r1_{b}"]), ACT_RELU, ring[(k + 1) % len(ring)], Feat(g.d[f"h{b}"]),
+                   dh, accumulate=True, padbuf=padbuf, pend=pend)
+            if ngrp:
+                flush(False)
+            else:
+                ready(f"{ra.key}.weight")
+        if ngrp:
+            flush(True)
         self._fp8_roll(st, "res", "dy")   # next step's backward-data scales
         # down2 (+ blur-down)
         if self.no_aa:

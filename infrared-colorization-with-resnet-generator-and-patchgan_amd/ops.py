@@ -105,22 +105,27 @@ class LaunchTimer:
         self.pending = []
         self.enabled = False
 
-    def wrap(self, tag, fn):
+    def wrap(self, tag, fn, count=0):
+        """count > 0: the launch does the work of that many launches of ``tag`` (a grouped weight
+        gradient): it is recorded as ``count`` launches of elapsed / count each, and not at all
+        when fn returns False (nothing ran)."""
         if not self.enabled or (self.tags is not None and tag not in self.tags):
             return fn()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         out = fn()
+        if count and out is False:
+            return out
         b.record()
-        self.pending.append((tag, a, b))
+        self.pending.append((tag, a, b, count or 1))
         return out
 
     def summary(self):
         torch.cuda.synchronize()
         agg = {}
-        for tag, a, b in self.pending:
+        for tag, a, b, count in self.pending:
             n, t = agg.get(tag, (0, 0.0))
-            agg[tag] = (n + 1, t + a.elapsed_time(b))
+            agg[tag] = (n + count, t + a.elapsed_time(b))
         return {k: (n, t / n) for k, (n, t) in agg.items()}  # (launches, mean ms)
 
 
@@ -560,7 +565,45 @@ def conv_wgrad(spec: ConvSpec, x: Feat, dy: Feat, dw: torch.Tensor, dtype: int, 
         stream()))
 
 
-WGRAD_WS_FLOATS = 24 << 20   # split-K slab workspace (96 MB): >= slots x tile for every layer of the step
+WGRAD_GROUP_MAX = 4   # W2_GROUP_MAX (csrc/conv_wgrad_pc.hip)
+# ResnetBlock weight gradients per grouped launch in GeneratorEngine.backward; 0: per-layer
+# launches (IRGAN_NO_WGRAD_GROUP=1, the A/B switch).  4: the fastest of 2, 3, 4 in the 256^2
+# B = 16 step and per layer (profiles/wgrad_group.txt)
+WGRAD_GROUP = [0 if os.environ.get("IRGAN_NO_WGRAD_GROUP") else 4]
+
+
+def set_wgrad_group(n: int) -> int:
+    """Group size of the deferred ResnetBlock weight gradients (0: per-layer launches).
+    Returns the previous setting."""
+    assert 0 <= n <= WGRAD_GROUP_MAX
+    old, WGRAD_GROUP[0] = WGRAD_GROUP[0], int(n)
+    return old
+
+
+def conv_wgrad_group(spec: ConvSpec, xs, dys, dws, dtype: int, ws: torch.Tensor = None) -> bool:
+    """dws[i] += weight gradient of conv(xs[i]) given dys[i], all of one shape and slicing, in
+    one launch and one ordered reduce (irgan_conv_wgrad_group).  False: the library does not
+    take the group (shape, dtype, count, workspace) and NOTHING ran.  ``ws``: the split-K slab
+    (default: the stream's wgrad workspace).  Out of deterministic mode each problem is split
+    1 / n as many ways as alone (fewer fp32 partials per element); in it every problem keeps its
+    own splits, so each dw is conv_wgrad's bit for bit whatever n."""
+    n = len(xs)
+    assert n == len(dys) == len(dws) and n >= 1
+    x, dy = xs[0], dys[0]
+    for a, b, dw in zip(xs, dys, dws):
+        assert a.t.shape == x.t.shape and a.off == x.off and b.t.shape == dy.t.shape and b.off == dy.off
+        assert b.C == spec.cout and a.C >= spec.cin and a.dt == dtype and b.dt == dtype and dw.dtype == torch.float32
+    d = _fwd_desc(spec, x, dy, spec.cin, dtype, F32, accumulate=1, flags=CONV_DETERMINISTIC if _DET[0] else 0)
+    if ws is None:
+        ws = _wgrad_ws(dws[0].device)
+    arr = ctypes.c_void_p * n
+    px, pdy, pdw = arr(*(a.t.data_ptr() for a in xs)), arr(*(b.t.data_ptr() for b in dys)), \
+        arr(*(w.data_ptr() for w in dws))
+    return TIMER.wrap(conv_tag("wgrad", spec, (x.H, x.W), x.N), lambda: _try(
+        "irgan_conv_wgrad_group", ctypes.byref(d), n, px, pdy, pdw, P(ws), ws.numel(), stream()), count=n)
+
+
+WGRAD_WS_FLOATS = 24 << 20  # split-K slab workspace (96 MB): >= slots x tile for every layer of the step
 _WGRAD_WS = {}
 
 
