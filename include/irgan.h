@@ -578,6 +578,36 @@ IRGAN_API int irgan_adam_ema_prep(int32_t* count, double lr, double beta1, doubl
                    float* prm, irgan_stream_t s);
 IRGAN_API int irgan_adam_ema_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
                    const float* prm, float beta1, float beta2, float eps, irgan_stream_t s);
+/* ---- gradient-norm clipping (torch.nn.utils.clip_grad_norm_(params, max_norm, 2) in front
+ * of the optimizer step) inside the Adam launch: norm = sqrt(sum g^2) over the whole flat
+ * buffer, coef = min(1, max_norm / (norm + 1e-6)), Adam consumes g * coef (one fp32 product,
+ * rounded; g itself is only read and stays unscaled).  Non-finite norms get no special
+ * handling.
+ * irgan_grad_sumsq: deterministic sum of squares of g[0..n) (any 4-byte-aligned pointer,
+ * 16-byte loads between a scalar head and tail): irgan_grad_sumsq_parts(n) blocks (a function
+ * of n alone, 0 for n <= 0, never an error code) each accumulate in fp64, combine in a fixed
+ * order and write one fp64 partial -- no atomics, so the same buffer gives the same bits on
+ * every launch and every data-parallel rank.  partials holds nparts doubles; a null pointer,
+ * n <= 0 or nparts != irgan_grad_sumsq_parts(n) is IRGAN_EINVAL and launches nothing. */
+IRGAN_API int irgan_grad_sumsq_parts(int64_t n);
+IRGAN_API int irgan_grad_sumsq(const float* g, int64_t n, double* partials, int32_t nparts, irgan_stream_t s);
+/* irgan_adam_ema_prep's count and prm[0..2] (ema_decay 0 where there is no average) and, from
+ * the partials of a buffer of n elements added in index order in fp64, *norm_out = norm (fp64,
+ * device, nullable) and prm[3] = coef rounded to fp32: its prm holds FOUR floats.  IRGAN_EINVAL
+ * (nothing launched): a null count / prm / partials, ema_decay outside [0, 1), max_norm not
+ * > 0, n <= 0, nparts != irgan_grad_sumsq_parts(n). */
+IRGAN_API int irgan_adam_clip_prep(int32_t* count, double lr, double beta1, double beta2, double ema_decay,
+                   const double* partials, int32_t nparts, int64_t n, double max_norm, double* norm_out,
+                   float* prm, irgan_stream_t s);
+/* The Adam entries above on g * coef: coef from prm[3] (irgan_adam_clip_dev) or from the host
+ * (irgan_adam_clip).  ema may be NULL: then no average is touched (and ema_weight ignored).
+ * p, m, v and ema are bit-identical to the unclipped entries run on a gradient buffer that
+ * holds the fp32 products g * coef. */
+IRGAN_API int irgan_adam_clip_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                   const float* prm, float beta1, float beta2, float eps, irgan_stream_t s);
+IRGAN_API int irgan_adam_clip(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float step_size,
+                   float beta1, float beta2, float bc2_sqrt, float eps, float ema_weight, float coef,
+                   irgan_stream_t s);
 
 /* ---- inference / evaluation ---- */
 /* out[p][c] = uint8(clip((x + 1) / 2, 0, 1) * 255) for every pixel p and

@@ -1,12 +1,15 @@
 """``python -m infrared-colorization-with-resnet-generator-and-patchgan_amd [train|test]
-[--img-size N | HxW | native] [--load-size N | HxW | native] [--ema-decay D]`` -- the reference's script
+[--img-size N | HxW | native] [--load-size N | HxW | native] [--ema-decay D] [--clip-grad-G X]
+[--clip-grad-D X]`` -- the reference's script
 entry point (ir:1730-1756) with cfg.mode taken from the command line (default: Config's "test").
 ``--img-size`` sets cfg.img_size: N for N x N, HxW (height first, e.g. 512x640) or ``native`` for
 every frame at its own size; ``--load-size`` sets cfg.load_size, the training crop jitter: every
 training pair is resized to N x N, HxW or (``native``) left at its own size, and a random
 cfg.img_size window of it is the sample (e.g. ``--load-size 286`` with the default 256; validation
 and test ignore it); ``--ema-decay`` sets cfg.ema_decay (e.g. 0.999: train with a moving average
-of the generator weights).  Without a flag Config's value stands."""
+of the generator weights); ``--clip-grad-G`` / ``--clip-grad-D`` set cfg.clip_grad_G / cfg.clip_grad_D, the
+maximal L2 norm of the generator's / discriminator's gradient (clipped inside the fused Adam update,
+the norms join the step log).  Without a flag Config's value stands."""
 import argparse
 import sys
 
@@ -20,6 +23,8 @@ def config_from_argv(argv):
     ap.add_argument("--img-size", type=parse_img_size, default=argparse.SUPPRESS, metavar="N|HxW|native")
     ap.add_argument("--load-size", type=parse_load_size, default=argparse.SUPPRESS, metavar="N|HxW|native")
     ap.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, metavar="D")
+    ap.add_argument("--clip-grad-G", type=float, default=argparse.SUPPRESS, metavar="X", dest="clip_grad_G")
+    ap.add_argument("--clip-grad-D", type=float, default=argparse.SUPPRESS, metavar="X", dest="clip_grad_D")
     a = ap.parse_args(argv)
     cfg = Config()
     if a.mode is not None:
@@ -30,6 +35,9 @@ def config_from_argv(argv):
         cfg.load_size = a.load_size
     if hasattr(a, "ema_decay"):
         cfg.ema_decay = a.ema_decay
+    for name in ("clip_grad_G", "clip_grad_D"):
+        if hasattr(a, name):
+            setattr(cfg, name, getattr(a, name))
     return cfg
 
 

@@ -360,33 +360,48 @@ IRGAN_HD float ema_update(float ei, float pn, float we) {
     return __builtin_fmaf(we, pn - ei, ei);
 }
 
+// The clipped gradient g * coef: ONE fp32 product, rounded before adam_update sees it (torch's
+// g.mul_(coef) followed by the optimizer step).  Pinned like adam_update: left to the compiler
+// the product would fuse into the first moment's g - m.
+template <bool CLIP>
+IRGAN_HD float clip_grad(float gi, float coef) {
+#pragma clang fp contract(off)
+    if (!CLIP) return gi;
+    return gi * coef;
+}
+
 // Adam (4 reads, 3 writes per element) and, with e (EMA), the exponential moving average of
 // the new parameters, e += we * (p_new - e), in the same pass (5 reads, 4 writes).
 // prm (device, nullable): {step_size, bc2s} and, EMA, {.., we}, written by adam_prep_kernel in
 // the same stream (graph replay: the step count lives on the device, so a captured step stays
 // valid).  Without EMA neither e nor prm[2] nor we is touched.
+// CLIP (gradient-norm clipping): the update consumes g * coef, coef from prm[3]
+// (adam_clip_prep_kernel) or from the host; g itself is only read.  Without CLIP neither
+// prm[3] nor coef is touched.
 struct AdamArgs {
     float *p, *m, *v, *e;
     const float* g;
     const float* prm;
-    float step_size, b1, b2, bc2s, eps, we;
+    float step_size, b1, b2, bc2s, eps, we, coef;
 };
 
-template <bool EMA>
-IRGAN_HD void adam_coeffs(const AdamArgs& a, float& step_size, float& bc2s, float& we) {
-    step_size = a.step_size, bc2s = a.bc2s, we = a.we;
+template <bool EMA, bool CLIP>
+IRGAN_HD void adam_coeffs(const AdamArgs& a, float& step_size, float& bc2s, float& we, float& coef) {
+    step_size = a.step_size, bc2s = a.bc2s, we = a.we, coef = a.coef;
     if (a.prm) {
         step_size = a.prm[0];
         bc2s = a.prm[1];
         if (EMA) we = a.prm[2];
+        if (CLIP) coef = a.prm[3];
     }
 }
 
-template <bool EMA>
-IRGAN_HD void adam_one(const AdamArgs& a, long i, float step_size, float w1, float w2, float bc2s, float we) {
+template <bool EMA, bool CLIP>
+IRGAN_HD void adam_one(const AdamArgs& a, long i, float step_size, float w1, float w2, float bc2s, float we,
+                       float coef) {
     float mi = a.m[i], vi = a.v[i];
     const float ei = EMA ? a.e[i] : 0.f;
-    const float pn = adam_update(a.p[i], a.g[i], mi, vi, step_size, w1, a.b2, w2, bc2s, a.eps);
+    const float pn = adam_update(a.p[i], clip_grad<CLIP>(a.g[i], coef), mi, vi, step_size, w1, a.b2, w2, bc2s, a.eps);
     a.p[i] = pn;
     a.m[i] = mi;
     a.v[i] = vi;
@@ -394,22 +409,22 @@ IRGAN_HD void adam_one(const AdamArgs& a, long i, float step_size, float w1, flo
 }
 
 // any 4-byte-aligned pointers: one element per thread and round
-template <bool EMA>
+template <bool EMA, bool CLIP>
 __global__ __launch_bounds__(TPB) void adam_kernel(AdamArgs a, long n) {
-    float step_size, bc2s, we;
-    adam_coeffs<EMA>(a, step_size, bc2s, we);
+    float step_size, bc2s, we, coef;
+    adam_coeffs<EMA, CLIP>(a, step_size, bc2s, we, coef);
     const float w1 = 1.f - a.b1, w2 = 1.f - a.b2;
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB)
-        adam_one<EMA>(a, i, step_size, w1, w2, bc2s, we);
+        adam_one<EMA, CLIP>(a, i, step_size, w1, w2, bc2s, we, coef);
 }
 
 // The pointers share one offset from a 16-byte boundary: `head` (< 4) leading elements and
 // the tail (< 4) one per thread (block 0), the nvec groups of four between them with
 // 16-byte loads and stores, grid-stride.  n = head + 4 * nvec + tail.
-template <bool EMA>
+template <bool EMA, bool CLIP>
 __global__ __launch_bounds__(TPB) void adam_vec_kernel(AdamArgs a, int head, long nvec, int tail) {
-    float step_size, bc2s, we;
-    adam_coeffs<EMA>(a, step_size, bc2s, we);
+    float step_size, bc2s, we, coef;
+    adam_coeffs<EMA, CLIP>(a, step_size, bc2s, we, coef);
     const float w1 = 1.f - a.b1, w2 = 1.f - a.b2;
     float4* __restrict__ p4 = reinterpret_cast<float4*>(a.p + head);
     float4* __restrict__ m4 = reinterpret_cast<float4*>(a.m + head);
@@ -419,7 +434,13 @@ __global__ __launch_bounds__(TPB) void adam_vec_kernel(AdamArgs a, int head, lon
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < nvec; i += (long)gridDim.x * TPB) {
         float4 P = p4[i], M = m4[i], V = v4[i], E;
         if (EMA) E = e4[i];
-        const float4 G = g4[i];
+        float4 G = g4[i];
+        if (CLIP) {
+            G.x = clip_grad<CLIP>(G.x, coef);
+            G.y = clip_grad<CLIP>(G.y, coef);
+            G.z = clip_grad<CLIP>(G.z, coef);
+            G.w = clip_grad<CLIP>(G.w, coef);
+        }
         P.x = adam_update(P.x, G.x, M.x, V.x, step_size, w1, a.b2, w2, bc2s, a.eps);
         P.y = adam_update(P.y, G.y, M.y, V.y, step_size, w1, a.b2, w2, bc2s, a.eps);
         P.z = adam_update(P.z, G.z, M.z, V.z, step_size, w1, a.b2, w2, bc2s, a.eps);
@@ -437,33 +458,86 @@ __global__ __launch_bounds__(TPB) void adam_vec_kernel(AdamArgs a, int head, lon
     }
     if (blockIdx.x == 0 && (int)threadIdx.x < head + tail) {
         const int t = threadIdx.x;
-        adam_one<EMA>(a, t < head ? (long)t : (long)head + 4 * nvec + (t - head), step_size, w1, w2, bc2s, we);
+        adam_one<EMA, CLIP>(a, t < head ? (long)t : (long)head + 4 * nvec + (t - head), step_size, w1, w2, bc2s, we,
+                            coef);
     }
 }
 
-// EMA iff a.e.  16-byte accesses when the pointers that exist (four, with EMA five) share one
+// One arm of the path below: the 16-byte kernel when the pointers allow (vec), else one element
+// per lane.
+template <bool EMA, bool CLIP>
+void adam_arm(const AdamArgs& a, long n, bool vec, long head, long nvec, int tail, hipStream_t st) {
+    if (vec)
+        adam_vec_kernel<EMA, CLIP><<<nblocks(nvec), TPB, 0, st>>>(a, (int)head, nvec, tail);
+    else
+        adam_kernel<EMA, CLIP><<<nblocks(n), TPB, 0, st>>>(a, n);
+}
+
+// EMA iff a.e; clip: the gradient times prm[3] / a.coef.  16-byte accesses when the pointers
+// that exist (four, with EMA five) share one
 // offset from a 16-byte boundary and there is a whole group of four; one element per lane
 // otherwise.  The vector kernel takes one group of four per thread under nblocks' cap: a full
 // round of its grid is 8192 * TPB * 4 elements, the rest grid-strides.
-int adam_launch(const AdamArgs& a, long n, hipStream_t st) {
+int adam_launch(const AdamArgs& a, long n, hipStream_t st, bool clip = false) {
     const uintptr_t off = (uintptr_t)a.p % 16;
     auto at_off = [off](const float* q) { return (uintptr_t)q % 16 == off; };
     const bool same = at_off(a.g) && at_off(a.m) && at_off(a.v) && (!a.e || at_off(a.e)) && off % 4 == 0;
     const long head = std::min<long>(n, (16 - (long)off) % 16 / 4);
     const long nvec = (n - head) / 4;
     const int tail = (int)(n - head - 4 * nvec);
-    if (same && nvec > 0) {
-        if (a.e)
-            adam_vec_kernel<true><<<nblocks(nvec), TPB, 0, st>>>(a, (int)head, nvec, tail);
-        else
-            adam_vec_kernel<false><<<nblocks(nvec), TPB, 0, st>>>(a, (int)head, nvec, tail);
-    } else if (a.e) {
-        adam_kernel<true><<<nblocks(n), TPB, 0, st>>>(a, n);
-    } else {
-        adam_kernel<false><<<nblocks(n), TPB, 0, st>>>(a, n);
-    }
+    const bool vec = same && nvec > 0;
+    if (a.e && clip)
+        adam_arm<true, true>(a, n, vec, head, nvec, tail, st);
+    else if (a.e)
+        adam_arm<true, false>(a, n, vec, head, nvec, tail, st);
+    else if (clip)
+        adam_arm<false, true>(a, n, vec, head, nvec, tail, st);
+    else
+        adam_arm<false, false>(a, n, vec, head, nvec, tail, st);
     IRGAN_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- gradient-norm clipping: the sum of squares of a flat fp32 buffer, deterministic ----
+// The grid is a function of n alone (sumsq_parts), every thread accumulates g*g in fp64 (the
+// square of an fp32 is exact there, and 1e25 does not overflow), a block combines its threads
+// in a fixed tree and writes ONE fp64 partial; adam_clip_prep_kernel adds the partials in index
+// order.  No atomics: the same buffer gives the same bits on every launch and every rank, so
+// the data-parallel replicas clip by the same coefficient.
+constexpr int SUMSQ_MAX_PARTS = 1024;   // partials of one buffer: the prep kernel holds them in LDS
+
+int sumsq_parts(long n) {
+    return (int)std::max<long>(1, std::min<long>((n + 4L * TPB - 1) / (4L * TPB), SUMSQ_MAX_PARTS));
+}
+
+// g: any 4-byte-aligned pointer.  `head` (< 4) elements up to the 16-byte boundary and the tail
+// (< 4) one per thread (block 0), the nvec groups of four between them with 16-byte loads,
+// grid-stride.  n = head + 4 * nvec + tail.
+__global__ __launch_bounds__(TPB) void sumsq_kernel(const float* __restrict__ g, int head, long nvec, int tail,
+                                                    double* __restrict__ partials) {
+    __shared__ double red[TPB];
+    auto sq = [](float x) { return (double)x * (double)x; };
+    double acc = 0.0;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + head);
+#pragma unroll 4
+    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < nvec; i += (long)gridDim.x * TPB) {
+        const float4 G = g4[i];
+        acc += sq(G.x);
+        acc += sq(G.y);
+        acc += sq(G.z);
+        acc += sq(G.w);
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < head + tail) {
+        const int t = threadIdx.x;
+        acc += sq(g[t < head ? (long)t : (long)head + 4 * nvec + (t - head)]);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = TPB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
 template <int K>
@@ -585,8 +659,7 @@ extern "C" int irgan_ssim(const float* a, const float* b, int32_t N, int32_t H, 
 // arguments (ops.adam), in fp64 and then rounded to fp32, evaluated on the device.
 // EMA (irgan_adam_ema_prep): also prm[2] = 1 - min(decay, (1 + t) / (10 + t)) (ops.ema_weight).
 template <bool EMA>
-static __global__ void adam_prep_kernel(int32_t* count, double lr, double b1, double b2, double decay, float* prm) {
-    if (threadIdx.x != 0) return;
+IRGAN_HD void adam_prep_body(int32_t* count, double lr, double b1, double b2, double decay, float* prm) {
     const int t = *count + 1;
     *count = t;
     const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
@@ -596,6 +669,33 @@ static __global__ void adam_prep_kernel(int32_t* count, double lr, double b1, do
         const double warm = (1.0 + (double)t) / (10.0 + (double)t);
         prm[2] = (float)(1.0 - (decay < warm ? decay : warm));
     }
+}
+
+template <bool EMA>
+static __global__ void adam_prep_kernel(int32_t* count, double lr, double b1, double b2, double decay, float* prm) {
+    if (threadIdx.x != 0) return;
+    adam_prep_body<EMA>(count, lr, b1, b2, decay, prm);
+}
+
+// The clip form (irgan_adam_clip_prep): the same count and prm[0..2] (the EMA weight always: a
+// decay of 0 where there is no average), and from sumsq_kernel's partials, added in index order
+// in fp64: norm = sqrt(sum) -> *norm_out (fp64, nullable), prm[3] = min(1, max_norm / (norm + 1e-6))
+// rounded to fp32 -- torch.nn.utils.clip_grad_norm_'s coefficient.  A non-finite norm gets what
+// the formula gives (NaN stays NaN, inf gives 0), as with torch's error_if_nonfinite=False.
+static __global__ void adam_clip_prep_kernel(int32_t* count, double lr, double b1, double b2, double decay,
+                                             float* prm, const double* __restrict__ partials, int nparts,
+                                             double max_norm, double* norm_out) {
+    __shared__ double part[SUMSQ_MAX_PARTS];
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x) part[i] = partials[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    adam_prep_body<true>(count, lr, b1, b2, decay, prm);
+    double s = 0.0;
+    for (int i = 0; i < nparts; ++i) s += part[i];
+    const double norm = sqrt(s);
+    if (norm_out) *norm_out = norm;
+    const double coef = max_norm / (norm + 1e-6);
+    prm[3] = (float)(coef > 1.0 ? 1.0 : coef);
 }
 
 extern "C" int irgan_adam_prep(int32_t* count, double lr, double beta1, double beta2, float* prm, irgan_stream_t s) {
@@ -640,4 +740,42 @@ extern "C" int irgan_adam_ema(float* p, const float* g, float* m, float* v, floa
     if (n <= 0) return 0;
     return adam_launch(AdamArgs{p, m, v, ema, g, nullptr, step_size, beta1, beta2, bc2_sqrt, eps, ema_weight},
                            n, (hipStream_t)s);
+}
+
+// ---- gradient-norm clipping (include/irgan.h) ----
+extern "C" int irgan_grad_sumsq_parts(int64_t n) { return n > 0 ? sumsq_parts(n) : 0; }
+
+extern "C" int irgan_grad_sumsq(const float* g, int64_t n, double* partials, int32_t nparts, irgan_stream_t s) {
+    if (!g || !partials || n <= 0 || nparts != sumsq_parts(n)) return IRGAN_EINVAL;
+    const long head = std::min<long>(n, (16 - (long)((uintptr_t)g % 16)) % 16 / 4);
+    const long nvec = (n - head) / 4;
+    sumsq_kernel<<<nparts, TPB, 0, (hipStream_t)s>>>(g, (int)head, nvec, (int)(n - head - 4 * nvec), partials);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_adam_clip_prep(int32_t* count, double lr, double beta1, double beta2, double ema_decay,
+                                    const double* partials, int32_t nparts, int64_t n, double max_norm,
+                                    double* norm_out, float* prm, irgan_stream_t s) {
+    if (!count || !prm || !partials || !(ema_decay >= 0.0 && ema_decay < 1.0) || !(max_norm > 0.0)) return IRGAN_EINVAL;
+    if (n <= 0 || nparts != sumsq_parts(n)) return IRGAN_EINVAL;
+    adam_clip_prep_kernel<<<1, 256, 0, (hipStream_t)s>>>(count, lr, beta1, beta2, ema_decay, prm, partials, nparts,
+                                                         max_norm, norm_out);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_adam_clip_dev(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                                   const float* prm, float beta1, float beta2, float eps, irgan_stream_t s) {
+    if (!prm) return IRGAN_EINVAL;
+    if (n <= 0) return 0;
+    return adam_launch(AdamArgs{p, m, v, ema, g, prm, 0.f, beta1, beta2, 1.f, eps, 0.f, 1.f}, n, (hipStream_t)s, true);
+}
+
+extern "C" int irgan_adam_clip(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float step_size,
+                               float beta1, float beta2, float bc2_sqrt, float eps, float ema_weight, float coef,
+                               irgan_stream_t s) {
+    if (n <= 0) return 0;
+    return adam_launch(AdamArgs{p, m, v, ema, g, nullptr, step_size, beta1, beta2, bc2_sqrt, eps, ema_weight, coef},
+                       n, (hipStream_t)s, true);
 }

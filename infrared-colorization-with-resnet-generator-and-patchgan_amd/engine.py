@@ -162,6 +162,7 @@ class ParamStore:
         self.dev_adam = False   # GANStep: step count on the device (irgan_adam_prep)
         self._count = self._prm = None
         self._count_host = 0
+        self._clip_ws = None    # adam_begin(max_norm=): the norm reduction's fp64 partials
 
     def krsc(self, k, buf=None):
         buf = self.flat if buf is None else buf
@@ -241,8 +242,8 @@ class ParamStore:
             raise RuntimeError(f"per-parameter Adam step counts differ: {sorted(steps)}")
         self.step_count = steps.pop()
 
-    def adam_step(self, lr, b1=0.5, b2=0.999, eps=1e-8):
-        self.adam_begin(lr, b1, b2, eps)(0, self.numel)
+    def adam_step(self, lr, b1=0.5, b2=0.999, eps=1e-8, max_norm=0.0):
+        self.adam_begin(lr, b1, b2, eps, max_norm=max_norm)(0, self.numel)
 
     @torch.no_grad()
     def enable_ema(self):
@@ -261,22 +262,28 @@ class ParamStore:
         self.flat.copy_(self.ema)
         self.ema.copy_(tmp)
 
-    def adam_begin(self, lr, b1=0.5, b2=0.999, eps=1e-8, ema_decay=0.0):
+    def adam_begin(self, lr, b1=0.5, b2=0.999, eps=1e-8, ema_decay=0.0, max_norm=0.0, norm_out=None):
         """Count one optimizer step and return apply(start, end), the Adam update of
         the flat slice [start, end): a step may be applied bucket by bucket as each
         bucket's gradient all-reduce completes (BucketedAllreduce.finish).  With ``ema_decay``
         and an ``ema`` buffer the same launch also moves ema[start:end] towards the new
-        parameters (ops.ema_weight); otherwise ``ema`` is not touched."""
+        parameters (ops.ema_weight); otherwise ``ema`` is not touched.
+
+        ``max_norm`` > 0 clips by the global L2 norm (torch.nn.utils.clip_grad_norm_ in front of
+        the optimizer step): the norm is taken over the WHOLE ``grad`` buffer when apply runs,
+        so apply is marked ``whole`` and takes (0, numel) only, once, after the gradient is
+        final; Adam consumes grad * coef in its own launch and ``grad`` stays unscaled.
+        ``norm_out`` (fp64[1] on the device, optional) receives the norm."""
         ema = self.ema if ema_decay else None
         self.step_count += 1
         t = self.step_count
+        if max_norm:
+            return self._adam_begin_clip(t, lr, b1, b2, eps, ema, ema_decay, float(max_norm), norm_out)
         if self.dev_adam:
             # the count and the bias corrections on the device (a captured step replays with
             # the right t); the device count is resynced to the host's after a state load
             if self._count is None:
-                self._count = torch.zeros(1, dtype=torch.int32, device=self.device)
-                self._prm = torch.zeros(3, dtype=torch.float32, device=self.device)  # the third: EMA weight
-                self._count_host = 0
+                self._dev_state()
             if self._count_host != t - 1:
                 self._count.fill_(t - 1)
             ops.adam_prep(self._count, lr, b1, b2, self._prm, None if ema is None else ema_decay)
@@ -290,6 +297,45 @@ class ParamStore:
         def apply(a, b):
             ops.adam(self.flat[a:b], self.grad[a:b], self.m[a:b], self.v[a:b], t, lr, b1, b2, eps,
                      None if ema is None else ema[a:b], ema_decay)
+        return apply
+
+    def _dev_state(self):
+        """The device step count and the Adam launches' coefficients, allocated once."""
+        self._count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # {step_size, bc2_sqrt, EMA weight, clip coefficient}: the last two written only when used
+        self._prm = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._count_host = 0
+
+    def _adam_begin_clip(self, t, lr, b1, b2, eps, ema, ema_decay, max_norm, norm_out):
+        """adam_begin with ``max_norm``: reduction over the whole buffer -> coefficient -> Adam,
+        queued when apply runs.  Device count: the clip form of the prep (ops.adam_clip_prep)
+        sums the partials, so there is no host sync and no launch beyond the reduction.  Host
+        count (ParamStore.adam_step users): the norm is read back (ops.grad_norm, one sync)."""
+        if self._clip_ws is None:
+            self._clip_ws = torch.zeros(ops.grad_sumsq_parts(self.numel), dtype=torch.float64, device=self.device)
+        ws, n = self._clip_ws, self.numel
+        if self.dev_adam:
+            if self._count is None:
+                self._dev_state()
+            if self._count_host != t - 1:
+                self._count.fill_(t - 1)
+            self._count_host = t
+
+        def apply(a, b):
+            if (a, b) != (0, n):
+                raise ValueError(f"a clipped Adam step is applied once over the whole buffer (0, {n}), got ({a}, {b})")
+            if self.dev_adam:
+                ops.grad_sumsq(self.grad, ws)
+                ops.adam_clip_prep(self._count, lr, b1, b2, self._prm, ws, n, max_norm, norm_out,
+                                   ema_decay if ema is not None else 0.0)
+                ops.adam_dev(self.flat, self.grad, self.m, self.v, self._prm, b1, b2, eps, ema, clip=True)
+                return
+            norm = ops.grad_norm(self.grad, ws)
+            if norm_out is not None:
+                norm_out.fill_(norm)
+            ops.adam(self.flat, self.grad, self.m, self.v, t, lr, b1, b2, eps, ema, ema_decay,
+                     coef=ops.clip_coef(norm, max_norm))
+        apply.whole = True
         return apply
 
 
@@ -1547,18 +1593,26 @@ class BucketedAllreduce:
         optimizer update of the bucket is queued behind its own collective and runs
         while the later buckets are still being reduced (the G-Adam of
         bucket k overlaps the all-reduce of bucket k+1).  Each element of the flat
-        buffer lies in exactly one bucket, so this is the whole-buffer mean + update."""
+        buffer lies in exactly one bucket, so this is the whole-buffer mean + update.
+
+        An ``apply`` marked ``whole`` (ParamStore.adam_begin with max_norm: the clipping norm
+        runs over the whole reduced buffer) is called once with (0, numel) after every bucket
+        has been waited for and scaled: that step gives up the Adam-under-all-reduce overlap,
+        and its norm does not depend on the bucket layout."""
         if not self.active:
             if apply is not None:
                 apply(0, self.store.numel)
             return
+        whole = apply is not None and getattr(apply, "whole", False)
         self._launch(0)
         for w, t, a, b in self.works:
             w.wait()
             if not self.avg:
                 t.div_(self.world)
-            if apply is not None:
+            if apply is not None and not whole:
                 apply(a, b)
+        if whole:
+            apply(0, self.store.numel)
         self.works, self.end = [], self.store.numel
 
 
@@ -1579,7 +1633,9 @@ def _mark(ph, key, stream):
 class GANStep:
     """Buffers, engines and the fused step for one rank.
 
-    Loss slots (fp64, device): 0 loss_D, 1 lambda_gan*GAN, 2 L1*l, 3 perc*l, 4 TV*l, 5 SSIM*l.
+    Loss slots (fp64, device): 0 loss_D, 1 lambda_gan*GAN, 2 L1*l, 3 perc*l, 4 TV*l, 5 SSIM*l;
+    6 / 7 the L2 norm of D's / G's (reduced, unclipped) gradient when that network clips
+    (Config.clip_grad_D / clip_grad_G), else 0.
     """
 
     def __init__(self, G: ParamStore, D: ParamStore, V: ParamStore, cfg, dtype=BF16, process_group=None,
@@ -1610,6 +1666,11 @@ class GANStep:
         # Config.ema_decay > 0: G's Adam launches also update G.ema (ParamStore.adam_begin); the
         # owner allocates it (G.enable_ema()), and 0 is the plain path with no buffer
         self.ema_decay = float(getattr(cfg, "ema_decay", 0.0) or 0.0)
+        # Config.clip_grad_G / clip_grad_D > 0: that network's Adam clips by the global gradient
+        # norm (ParamStore.adam_begin max_norm) and the norm lands in losses[7] / losses[6]; 0 is
+        # the plain path: no reduction, no extra launch, the slot stays 0
+        self.clip_G = float(getattr(cfg, "clip_grad_G", 0.0) or 0.0)
+        self.clip_D = float(getattr(cfg, "clip_grad_D", 0.0) or 0.0)
         # the D step (D forward/backward on [real; fake] and its all-reduce) runs on a
         # side stream, concurrently with the G-step terms that do not read D (L1,
         # VGG, TV, SSIM); IRGAN_NO_D_OVERLAP=1 keeps everything on one stream
@@ -1728,7 +1789,8 @@ class GANStep:
             # D Adam, then the G-step GAN term through the updated D (ir:1651, 1659-1662),
             # still on the side stream: the main stream meanwhile runs the G-step terms
             # that do not read D (L1, VGG, TV, SSIM)
-            self.d_reduce.finish(self.D.adam_begin(cfg.lr_D * self.lr_scale, cfg.beta1, cfg.beta2))
+            self.d_reduce.finish(self.D.adam_begin(cfg.lr_D * self.lr_scale, cfg.beta1, cfg.beta2,
+                                                   max_norm=self.clip_D, norm_out=L[6:7] if self.clip_D else None))
             self.dis.pack()
             # the G-step D pass reads cat([ir, fake]): the fake half of the D input (rewritten
             # when the D step saw the other dropout draw)
@@ -1748,7 +1810,8 @@ class GANStep:
         ops.axpby(dd.sl(cin, cout), 1.0, Feat(dfake), 1.0)
         self.gen.backward(dfake, ready=self.g_reduce.ready)
         self.g_reduce.finish(self.G.adam_begin(cfg.lr_G * self.lr_scale, cfg.beta1, cfg.beta2,
-                                               ema_decay=self.ema_decay))
+                                               ema_decay=self.ema_decay, max_norm=self.clip_G,
+                                               norm_out=L[7:8] if self.clip_G else None))
         self.gen.pack()
         if ph is not None:
             _mark(ph, "end", main)
@@ -1759,5 +1822,11 @@ class GANStep:
     def loss_dict(L: torch.Tensor, cfg) -> dict:
         v = L.tolist()
         gan = v[1] / cfg.lambda_gan if cfg.lambda_gan else 0.0
-        return dict(loss_D=v[0], loss_G=v[1] + v[2] + v[3] + v[4] + v[5], loss_G_GAN=gan, loss_G_L1=v[2],
-                    loss_G_perc=v[3], loss_G_TV=v[4], loss_G_ssim=v[5])
+        d = dict(loss_D=v[0], loss_G=v[1] + v[2] + v[3] + v[4] + v[5], loss_G_GAN=gan, loss_G_L1=v[2],
+                 loss_G_perc=v[3], loss_G_TV=v[4], loss_G_ssim=v[5])
+        # the gradient norms, only for the networks that clip (the key set is unchanged otherwise)
+        if getattr(cfg, "clip_grad_D", 0.0):
+            d["grad_norm_D"] = v[6]
+        if getattr(cfg, "clip_grad_G", 0.0):
+            d["grad_norm_G"] = v[7]
+        return d

@@ -109,6 +109,9 @@ class Config:
         self.load_size = None            # S, (height, width) or "native" (data.load_hw): train_kaist resizes each
                                          # training pair to this size and trains on a random img_size crop of it
                                          # (validation and run_test go straight to img_size); None = off
+        self.clip_grad_G = 0.0           # > 0: clip G's / D's gradient to this global L2 norm inside the fused
+        self.clip_grad_D = 0.0           # Adam launch (torch.nn.utils.clip_grad_norm_ semantics) and report the
+                                         # norm as grad_norm_G / grad_norm_D in GANTrainer.losses; 0 = off
 
 
 # =============================================================================
@@ -687,6 +690,19 @@ def _check_ema_decay(cfg):
     return d
 
 
+def _check_clip_grad(cfg):
+    """(Config.clip_grad_G, Config.clip_grad_D) as floats; ValueError unless finite and >= 0
+    (0 = off)."""
+    out = []
+    for name in ("clip_grad_G", "clip_grad_D"):
+        c = float(getattr(cfg, name, 0.0) or 0.0)
+        if not (math.isfinite(c) and c >= 0.0):
+            raise ValueError(f"{name} is the maximal gradient L2 norm, finite and >= 0 (0 turns clipping off), "
+                             f"got {c!r}")
+        out.append(c)
+    return tuple(out)
+
+
 class GANTrainer:
     """Owns G (through the model), D, VGG and both Adams; ``step(ir, rgb)`` runs
     the fused HIP train step and returns the device loss vector (no host sync)."""
@@ -698,6 +714,7 @@ class GANTrainer:
         self.cfg = cfg
         _refuse_multi_rank_batch_norm(cfg, process_group)   # before any GPU work
         self.ema_decay = _check_ema_decay(cfg)              # likewise
+        self.clip_grad_G, self.clip_grad_D = _check_clip_grad(cfg)
         dev = torch.device(cfg.device)
         dt = getattr(cfg, "compute_dtype", "bf16")
         if getattr(cfg, "deterministic", False):
@@ -990,7 +1007,9 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
                     f"D: {d['loss_D']:.4f} | G: {d['loss_G']:.4f} "
                     f"(GAN {d['loss_G_GAN']:.4f} + L1 {d['loss_G_L1']:.4f} "
                     f"+ Perc {d['loss_G_perc']:.4f} + TV {d['loss_G_TV']:.6f} "
-                    f"+ SSIM {d['loss_G_ssim']:.4f})")
+                    f"+ SSIM {d['loss_G_ssim']:.4f})"
+                    + "".join(f" | |grad {n}|: {d[k]:.4g}" for n, k in (("D", "grad_norm_D"), ("G", "grad_norm_G"))
+                              if k in d))
         avg = trainer.losses(acc / max(steps, 1))
         val_l1 = validate_kaist(model, val_loader, device)
         log(f"Epoch [{epoch}/{cfg.epochs}] DONE | avg D: {avg['loss_D']:.4f} | avg G: {avg['loss_G']:.4f} | "

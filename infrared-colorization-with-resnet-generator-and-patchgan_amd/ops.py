@@ -1164,15 +1164,63 @@ def _adam_call(form, p, g, m, v, ema, *args):
     _lib.call(f"irgan_adam_ema{form}", P(p), P(g), P(m), P(v), P(ema), p.numel(), *args, stream())
 
 
-def adam(p, g, m, v, step: int, lr: float, b1: float, b2: float, eps: float, ema=None, decay: float = 0.0):
+def _adam_clip_call(form, p, g, m, v, ema, *args):
+    """irgan_adam_clip<form>: one entry with and without ``ema`` (a null pointer)."""
+    if any(t.numel() != p.numel() for t in (g, m, v) + (() if ema is None else (ema,))):
+        raise ValueError(f"ops.adam{form}: p, g, m, v and ema must have one element count")
+    _lib.call(f"irgan_adam_clip{form}", P(p), P(g), P(m), P(v), P(ema), p.numel(), *args, stream())
+
+
+def adam(p, g, m, v, step: int, lr: float, b1: float, b2: float, eps: float, ema=None, decay: float = 0.0,
+         coef: float = None):
     """One Adam step with host-side bias corrections (irgan_adam).  With ``ema`` also, in the
     same pass, ema += ema_weight(decay, step) * (p_new - ema) (irgan_adam_ema); p, m, v come
-    out the same with and without it, bit for bit."""
+    out the same with and without it, bit for bit.  With ``coef`` (gradient-norm clipping,
+    clip_coef) the update consumes float32(g * float32(coef)); g is not written
+    (irgan_adam_clip)."""
     bc1 = 1 - b1 ** step
     bc2 = 1 - b2 ** step
+    head = (ctypes.c_float(lr / bc1), ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(math.sqrt(bc2)),
+            ctypes.c_float(eps))
+    if coef is not None:
+        return _adam_clip_call("", p, g, m, v, ema, *head,
+                               ctypes.c_float(0.0 if ema is None else ema_weight(decay, step)), ctypes.c_float(coef))
     tail = () if ema is None else (ctypes.c_float(ema_weight(decay, step)),)
-    _adam_call("", p, g, m, v, ema, ctypes.c_float(lr / bc1), ctypes.c_float(b1), ctypes.c_float(b2),
-               ctypes.c_float(math.sqrt(bc2)), ctypes.c_float(eps), *tail)
+    _adam_call("", p, g, m, v, ema, *head, *tail)
+
+
+def clip_coef(norm: float, max_norm: float) -> float:
+    """torch.nn.utils.clip_grad_norm_'s factor for a gradient of L2 norm ``norm``:
+    ``min(1, max_norm / (norm + 1e-6))`` in fp64 (NaN stays NaN); the kernels take it rounded
+    to fp32 (irgan_adam_clip_prep evaluates the same formula on the device)."""
+    c = float(max_norm) / (float(norm) + 1e-6)
+    return 1.0 if c > 1.0 else c
+
+
+def grad_sumsq_parts(n: int) -> int:
+    """The number of fp64 partials ops.grad_sumsq writes for n elements (a function of n alone)."""
+    return int(_lib.load().irgan_grad_sumsq_parts(int(n)))
+
+
+def grad_sumsq(g: torch.Tensor, partials: torch.Tensor):
+    """Deterministic sum of squares of the flat fp32 ``g`` as grad_sumsq_parts(n) fp64 per-block
+    partials (irgan_grad_sumsq): their sum IN INDEX ORDER is the squared L2 norm, the same bits
+    on every launch and every rank."""
+    if g.dtype != torch.float32 or partials.dtype != torch.float64:
+        raise ValueError("ops.grad_sumsq: g is fp32, partials fp64")
+    _lib.call("irgan_grad_sumsq", P(g), g.numel(), P(partials), partials.numel(), stream())
+
+
+def grad_norm(g: torch.Tensor, partials: torch.Tensor = None) -> float:
+    """The L2 norm of ``g`` on the host (one sync): ops.grad_sumsq's partials added in index
+    order in fp64, as irgan_adam_clip_prep adds them on the device."""
+    if partials is None:
+        partials = torch.empty(grad_sumsq_parts(g.numel()), dtype=torch.float64, device=g.device)
+    grad_sumsq(g, partials)
+    s = 0.0
+    for x in partials.tolist():
+        s += x
+    return math.sqrt(s)
 
 
 def adam_prep(count: torch.Tensor, lr: float, b1: float, b2: float, prm: torch.Tensor, decay: float = None):
@@ -1187,10 +1235,31 @@ def adam_prep(count: torch.Tensor, lr: float, b1: float, b2: float, prm: torch.T
     _lib.call("irgan_adam_ema_prep", P(count), *lrb, ctypes.c_double(decay), P(prm), stream())
 
 
-def adam_dev(p, g, m, v, prm: torch.Tensor, b1: float, b2: float, eps: float, ema=None):
+def adam_clip_prep(count: torch.Tensor, lr: float, b1: float, b2: float, prm: torch.Tensor, partials: torch.Tensor,
+                   n: int, max_norm: float, norm_out: torch.Tensor = None, decay: float = 0.0):
+    """ops.adam_prep's count and prm[:3] (``decay`` 0 where there is no average) and, from
+    ops.grad_sumsq's ``partials`` of a buffer of ``n`` elements: norm_out[0] = its L2 norm (fp64,
+    optional), prm[3] = clip_coef(norm, max_norm) -- prm holds four floats
+    (irgan_adam_clip_prep).  No launch beyond this one, no host sync."""
+    if prm.numel() < 4:
+        raise ValueError("ops.adam_clip_prep: prm holds four floats")
+    if partials.dtype != torch.float64 or (norm_out is not None and norm_out.dtype != torch.float64):
+        raise ValueError("ops.adam_clip_prep: partials and norm_out are fp64")
+    _lib.call("irgan_adam_clip_prep", P(count), ctypes.c_double(lr), ctypes.c_double(b1), ctypes.c_double(b2),
+              ctypes.c_double(decay), P(partials), partials.numel(), int(n), ctypes.c_double(max_norm), P(norm_out),
+              P(prm), stream())
+
+
+def adam_dev(p, g, m, v, prm: torch.Tensor, b1: float, b2: float, eps: float, ema=None, clip: bool = False):
     """ops.adam with step_size / bc2_sqrt and, with ``ema``, the EMA weight read from prm on the
-    device (irgan_adam_dev / irgan_adam_ema_dev)."""
-    _adam_call("_dev", p, g, m, v, ema, P(prm), ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(eps))
+    device (irgan_adam_dev / irgan_adam_ema_dev); with ``clip`` the gradient times prm[3]
+    (ops.adam_clip_prep; irgan_adam_clip_dev)."""
+    tail = (P(prm), ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(eps))
+    if clip:
+        if prm.numel() < 4:
+            raise ValueError("ops.adam_dev: with clip, prm holds four floats")
+        return _adam_clip_call("_dev", p, g, m, v, ema, *tail)
+    _adam_call("_dev", p, g, m, v, ema, *tail)
 
 
 # ----------------------------------------------------------------------------
