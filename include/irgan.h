@@ -494,6 +494,37 @@ IRGAN_API int irgan_sep_resample_fp8(const void* in, int32_t in_dtype, int32_t N
                            int32_t offo, const int32_t* ty, const float* wy, int32_t Ty,
                            const int32_t* tx, const float* wx, int32_t Tx, void* y8, int32_t ld8,
                            int32_t off8, const float* q, uint32_t* amax, irgan_stream_t s);
+/* The InstanceNorm backward of z = the pre-norm tensor whose act(IN(z)) a resample consumed in
+ * the forward (down1 / down2: conv -> IN -> ReLU -> Downsample, ir:469-482), taken from the
+ * resample's ADJOINT without storing its output: with da = bf16((Wy (x) Wx) dy) -- the bytes
+ * irgan_sep_resample writes for the same tables -- xhat = (z - mean) * rstd and g = da * act'(xhat),
+ *   _reduce: red[n][c] = {mean g, mean g * xhat}: irgan_in_bwd_reduce's row pass, partials and
+ *            fixed-order fp64 finalize, with da formed per pixel from its at most 2 x 2 taps
+ *            instead of loaded; nothing else is written;
+ *   _apply:  dz = rstd * (g - red.mean_g - xhat * red.mean_gxhat) from the adjoint launch itself.
+ * red and dz are bit for bit those of irgan_sep_resample + irgan_in_bwd_reduce + irgan_in_bwd_apply.
+ * dy: [N][Hin][Win] slice, tables [Hout][Ty] / [Wout][Tx] (the adjoint's: transpose = 1), z and dz
+ * [N][Hout][Wout] slices, mr z's {mean, rstd}.  work: IRGAN_IN_PARTS*N*C doubles, red: 2*N*C
+ * floats.  Deterministic, no atomics.  Both take the same shapes: IRGAN_EUNSUPPORTED -- nothing
+ * launched, nothing written -- unless everything is bf16, C, every ld and every off are
+ * multiples of 8, at most 2 taps per axis (the Downsample adjoint), and the pipelined row kernel
+ * takes the sizes (a [Win][C-group] fp32 row pair within 80 KiB of LDS, Win * G <= 1024 and
+ * Wout * G <= 2048 items for the 8-channel groups G of the C-group).
+ * The apply also refuses a dz that shares bytes with z, a bias gradient (db != NULL) and an e4m3
+ * copy (dz8 != NULL): the caller then runs irgan_sep_resample + irgan_in_bwd_reduce / _apply. */
+IRGAN_API int irgan_sep_resample_in_bwd_reduce(const void* dy, int32_t dy_dtype, int32_t N, int32_t Hin,
+                          int32_t Win, int32_t C, int32_t lddy, int32_t dyoff, int32_t Hout, int32_t Wout,
+                          const int32_t* ty, const float* wy, int32_t Ty, const int32_t* tx,
+                          const float* wx, int32_t Tx, const void* z, int32_t z_dtype, int32_t ldz,
+                          int32_t zoff, const float* mr, int32_t act, double* work, float* red,
+                          irgan_stream_t s);
+IRGAN_API int irgan_sep_resample_in_bwd_apply(const void* dy, int32_t dy_dtype, int32_t N, int32_t Hin,
+                          int32_t Win, int32_t C, int32_t lddy, int32_t dyoff, int32_t Hout, int32_t Wout,
+                          const int32_t* ty, const float* wy, int32_t Ty, const int32_t* tx,
+                          const float* wx, int32_t Tx, const void* z, int32_t z_dtype, int32_t ldz,
+                          int32_t zoff, const float* mr, int32_t act, const float* red, void* dz,
+                          int32_t dz_dtype, int32_t lddz, int32_t dzoff, float* db, void* dz8,
+                          irgan_stream_t s);
 /* 2x2 max pool (VGG features) forward / backward (first max wins, as ATen). */
 /* VGG conv + ReLU + MaxPool2d(2) in one launch (ir:664: vgg16.features[:16] conv1_2 -> pool):
  * y (NULL: not written) = act(conv(x) + bias) as irgan_conv_fwd, yp = its 2x2 max-pool, dense

@@ -283,6 +283,136 @@ void rows8_go(int key, const RowGrid& g, hipStream_t st, const RowArgs& a) {
     else rows8_launch<MODE, F8, 16, AMAX, Y16>(g, st, a);
 }
 
+// rows8_kernel<1> whose gradient is not loaded but made per pixel from a four times smaller one:
+// da = bf16((Wy (x) Wx) dy) at pixel (oy, ox) from at most 2 x 2 taps of dy (the Downsample
+// adjoint; irgan_sep_resample_in_bwd_reduce), in sep_pipe_kernel's order -- the vertical taps of
+// each tap column first, then the horizontal ones, zero-weight slots skipped, fused multiply-adds
+// from +0 -- so da is the bytes irgan_sep_resample stores and, the chains, block_reduce and the
+// partial layout being rows8_kernel<1>'s at the same (N, HW, C), the partials are the bits the
+// reduce pass over the stored da leaves.  The up-sampled gradient is never written or read; the
+// taps of neighbouring pixels share their 16-byte loads in the caches.  The block's slice of the
+// two tap tables (all Wout columns, the NR output rows its pixels lie in) sits in LDS, so a
+// pixel's tap addresses cost no memory round trip in front of its loads.
+template <int U>
+__global__ __launch_bounds__(TPB) void rows8_adjoint_reduce_kernel(
+    const bf16_t* __restrict__ x, int ldx, int xoff, const bf16_t* __restrict__ dy, int lddy, int dyoff, int Hin, int Win,
+    int W, const int* __restrict__ ty, const float* __restrict__ wy, int Ty, const int* __restrict__ tx,
+    const float* __restrict__ wx, int Tx, int act, const float* __restrict__ mr, int HW, int C, int rows_per_block,
+    int NR, float2* __restrict__ part) {
+    __shared__ float s0[TPB * 8], s1[TPB * 8];
+    extern __shared__ float4 tab4[];
+    float* const lwx = (float*)tab4;          // [W][2] horizontal weights, then taps
+    int* const lix = (int*)(lwx + 2 * W);
+    float* const lwy = (float*)(lix + 2 * W);   // [NR][2] vertical weights, then taps, from row oyb
+    int* const liy = (int*)(lwy + 2 * NR);
+    const int n = blockIdx.y;
+    const int r0 = blockIdx.x * rows_per_block;
+    const int r1 = min(HW, r0 + rows_per_block);
+    const int oyb = r0 / W, H = HW / W;
+    for (int e = threadIdx.x; e < 2 * W; e += TPB) {
+        const int o = e >> 1, i = e & 1;
+        lwx[e] = i < Tx ? wx[o * Tx + i] : 0.f;
+        lix[e] = i < Tx ? tx[o * Tx + i] : 0;
+    }
+    for (int e = threadIdx.x; e < 2 * NR; e += TPB) {
+        const int o = min(oyb + (e >> 1), H - 1), i = e & 1;
+        lwy[e] = i < Ty ? wy[o * Ty + i] : 0.f;
+        liy[e] = i < Ty ? ty[o * Ty + i] : 0;
+    }
+    __syncthreads();
+    Lay L(C, 8);
+    const bool active = L.rl < L.RP;
+    const long pb = (long)n * HW;
+    const float neg = act == IRGAN_ACT_RELU ? 0.f : act == IRGAN_ACT_LRELU ? 0.2f : 1.f;   // act_grad where xhat <= 0
+    for (int cb = 0; cb < C; cb += L.CL * 8) {
+        const int c = cb + L.cl * 8;
+        const bool on = active && c < C;
+        float a0[8], a1[8], mean[8], rstd[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { a0[k] = 0.f; a1[k] = 0.f; }
+        if (on) {
+            const float4* m4 = (const float4*)(mr + 2 * ((long)n * C + c));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 t = m4[k];
+                mean[2 * k] = t.x; rstd[2 * k] = t.y; mean[2 * k + 1] = t.z; rstd[2 * k + 1] = t.w;
+            }
+            uint4 xr[U], gr[U][2][2];
+            float wv[U][2], wh[U][2];
+            const int step = U * L.RP;
+#pragma unroll 1
+            for (int r = r0 + L.rl; r < r1; r += step) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {   // every load of the batch before any use
+                    const int q = min(r + u * L.RP, r1 - 1);
+                    const int oy = q / W, ox = q - oy * W;
+                    xr[u] = *(const uint4*)(x + (pb + q) * ldx + xoff + c);
+                    int iy[2], ix[2];
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        wv[u][i] = lwy[2 * (oy - oyb) + i];
+                        iy[i] = liy[2 * (oy - oyb) + i];
+                        wh[u][i] = lwx[2 * ox + i];
+                        ix[i] = lix[2 * ox + i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            gr[u][i][j] = wv[u][i] != 0.f && wh[u][j] != 0.f   // (a pixel has 1, 2 or 4 taps)
+                                              ? *(const uint4*)(dy + (((long)n * Hin + iy[i]) * Win + ix[j]) * lddy + dyoff + c)
+                                              : make_uint4(0u, 0u, 0u, 0u);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (r + u * L.RP >= r1) break;
+                    float xv[8], t[2][2][8];
+                    bf8f(xr[u], xv);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) bf8f(gr[u][i][j], t[i][j]);
+                    float o[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        float col[2];
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            col[j] = 0.f;
+#pragma unroll
+                            for (int i = 0; i < 2; ++i)
+                                if (wv[u][i] != 0.f) col[j] = __builtin_fmaf(wv[u][i], t[i][j][k], col[j]);
+                        }
+                        o[k] = 0.f;
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            if (wh[u][j] != 0.f) o[k] = __builtin_fmaf(wh[u][j], col[j], o[k]);
+                    }
+                    uint4 w;   // the stored bf16 of the plain launch
+                    w.x = pk_bf16(o[0], o[1]);
+                    w.y = pk_bf16(o[2], o[3]);
+                    w.z = pk_bf16(o[4], o[5]);
+                    w.w = pk_bf16(o[6], o[7]);
+                    float gv[8];
+                    bf8f(w, gv);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        // the contractions rows8_kernel<1> compiles to, spelled out (in_bwd_onepass_kernel)
+                        const float xh = (xv[k] - mean[k]) * rstd[k];
+                        const float f = xh > 0.f ? 1.f : neg;
+                        a0[k] = __builtin_fmaf(gv[k], f, a0[k]);
+                        a1[k] = __builtin_fmaf(gv[k] * f, xh, a1[k]);
+                    }
+                }
+            }
+        }
+        block_reduce<float, 8>(a0, a1, L, in_row_order(L.CL), on, cb, c, C, s0, s1,
+                               [=](int cc, int k, float t0, float t1) {
+            part[((long)n * gridDim.x + blockIdx.x) * C + cc + k] = make_float2(t0, t1);
+        });
+    }
+}
+
 // fp64 sum of the nb block partials of each (n, c): one block (FC channels x FS partial
 // lanes) per (image, channel group), the order is lane_combine's (deterministic).
 __global__ __launch_bounds__(256) void finalize_kernel(const float2* __restrict__ part, float* __restrict__ mr, int N,
@@ -747,6 +877,30 @@ extern "C" int irgan_in_bwd_reduce(const void* dy, int32_t dy_dtype, int32_t ldd
     const bool vec = vec_ok(C, {lddy, dyoff, ldx, xoff}) && (!dy2 || vec_ok(C, {lddy2, dy2off}));
     const int nb = launch_rows<1>(a, vec, st);
     finalize_kernel<<<dim3(irgan_cdiv(C, FC), N), 256, 0, st>>>((const float2*)work, red, N, C, nb, HW, 1);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// irgan_in_bwd_reduce over a gradient that is not stored: rows8_adjoint_reduce_kernel on the reduce
+// pass's own grid, then its finalize (resample.hip: irgan_sep_resample_in_bwd_reduce, which checks
+// the arguments -- all bf16, 8-channel vectors, at most 2 taps per axis; not exported)
+int in_bwd_reduce_adjoint_launch(const void* dy, int lddy, int dyoff, int Hin, int Win, const int* ty, const float* wy,
+                                 int Ty, const int* tx, const float* wx, int Tx, const void* z, int ldz, int zoff,
+                                 int act, int N, int Hout, int Wout, int C, const float* mr, double* work, float* red,
+                                 hipStream_t st) {
+    const int HW = Hout * Wout;
+    const RowGrid g = pass_grid(1, N, HW, C, V);
+    const int NR = (g.rows + Wout - 1) / Wout + 1;   // output rows a block's g.rows pixels can lie in
+    const size_t sh = (size_t)(2 * Wout + 2 * NR) * 8;
+    if (Ty > 2 || Tx > 2 || C % V || g.nb > IN_PARTS || sh > 40 * 1024) return IRGAN_EINVAL;
+#define ADJ(UV)                                                                                                    \
+    rows8_adjoint_reduce_kernel<UV><<<dim3(g.nb, N), TPB, sh, st>>>(                                               \
+        (const bf16_t*)z, ldz, zoff, (const bf16_t*)dy, lddy, dyoff, Hin, Win, Wout, ty, wy, Ty, tx, wx, Tx, act, mr, \
+        HW, C, g.rows, NR, (float2*)work)
+    if (irgan_cdiv(g.rows, g.RP) <= 1) ADJ(1);
+    else ADJ(2);
+#undef ADJ
+    finalize_kernel<<<dim3(irgan_cdiv(C, FC), N), 256, 0, st>>>((const float2*)work, red, N, C, g.nb, HW, 1);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -262,18 +262,38 @@ __global__ __launch_bounds__(NT) void sep_lds_kernel(const void* __restrict__ in
 //     the next row's barrier).
 // Same per-element arithmetic and tap order as sep_lds_kernel (bf16 in, bf16 out, no
 // accumulate; NORM / Q8 as there).  IPT / OPT: input / output items per thread (host-sized).
+//
+// EPI (irgan_sep_resample_in_bwd_apply): the mirror image of NORM on the output side -- the
+// InstanceNorm backward apply of the tensor z whose act(IN(z)) the FORWARD map consumed, taken
+// from this (adjoint) launch's output without storing it.  After the horizontal taps an item's 8
+// values are rounded to bf16 (the bytes the plain launch stores), z is read at the output
+// position, xhat = (z - mean) * rstd, g = v * act'(xhat), and dz = rstd * (g - mg - xhat * mgx),
+// {mg, mgx} from red, is stored in rows8_kernel<2>'s two fused steps through the same raw buffer
+// store: dz is bit for bit what the plain launch followed by irgan_in_bwd_apply writes.
+// Item k's z of row oy + 1 is loaded into the registers item k's z of row oy has just left
+// (OPT uint4 in all), one row ahead of its use like the vertical taps; past the last row the
+// load goes to the out-of-range offset, so a row's VMEM op count stays fixed.
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 int sep_swz();
+// (ints, not an unnamed enum: the kernel's mangled name spells the parameter type's condition)
+constexpr int EPI_NONE = 0, EPI_APPLY = 2;
+struct ResEpi {
+    const bf16_t* z;
+    int ld, off;
+    const float* red;
+};
 
-template <int TM, bool NORM, bool Q8, int IPT, int OPT, bool AMAX = true>
+template <int TM, bool NORM, bool Q8, int IPT, int OPT, bool AMAX = true, int EPI = EPI_NONE>
 __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict__ in, int Hin, int Win, int ldi,
                                                        int offi, bf16_t* __restrict__ out, int Hout, int Wout,
                                                        int ldo, int offo, const int* __restrict__ ty,
                                                        const float* __restrict__ wy, int Ty,
                                                        const int* __restrict__ tx, const float* __restrict__ wx,
                                                        int Tx, int CB, int CBP, int R, const float* __restrict__ mr,
-                                                       int C, int act, int swz, ResQ8 q8) {
+                                                       int C, int act, int swz,
+                                                       std::conditional_t<EPI != EPI_NONE, ResEpi, ResQ8> q8) {
+    static_assert(EPI == EPI_NONE || (!NORM && !Q8), "the output-side epilogue: plain loads, no e4m3 copy");
     constexpr int NT = 512;
     extern __shared__ float4 sm4[];
     float* const sm = (float*)sm4;                       // [2][Win][CBP] fp32 rows (CBP >= CB: bank spread)
@@ -312,8 +332,42 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
         (void*)in, (short)0, (int)((long)(n + 1) * Hin * Win * ldi * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
         out, (short)0, (int)((long)(n + 1) * Hout * Wout * ldo * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(
-        Q8 ? (void*)q8.p : (void*)out, (short)0, Q8 ? (int)((long)(n + 1) * Hout * Wout * q8.ld) : 0, 0x00020000);
+    void* qbase = (void*)out;
+    int qbytes = 0;
+    if constexpr (Q8) { qbase = (void*)q8.p; qbytes = (int)((long)(n + 1) * Hout * Wout * q8.ld); }
+    if constexpr (EPI != EPI_NONE) { qbase = (void*)q8.z; qbytes = (int)((long)(n + 1) * Hout * Wout * q8.ld * 2); }
+    const __amdgpu_buffer_rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(qbase, (short)0, qbytes, 0x00020000);
+    // EPI: this thread's octet of z's {mean, rstd} and of red's {mean g, mean g * xhat}, the
+    // derivative of act where xhat <= 0 (act_grad without its branches on act)
+    float em[EPI ? 8 : 1], er[EPI ? 8 : 1], eg[EPI ? 8 : 1], egx[EPI ? 8 : 1];
+    float eneg = 1.f;
+    uint4 zpre[EPI ? OPT : 1];
+    if constexpr (EPI != EPI_NONE) {
+        const long mi = 2 * ((long)n * C + c0 + (tid % G) * 8);
+        const float4* m4 = (const float4*)(mr + mi);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 t = m4[k];
+            em[2 * k] = t.x; er[2 * k] = t.y; em[2 * k + 1] = t.z; er[2 * k + 1] = t.w;
+        }
+        const float4* r4 = (const float4*)(q8.red + mi);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 t = r4[k];
+            eg[2 * k] = t.x; egx[2 * k] = t.y; eg[2 * k + 1] = t.z; egx[2 * k + 1] = t.w;
+        }
+        eneg = act == IRGAN_ACT_RELU ? 0.f : (act == IRGAN_ACT_LRELU ? 0.2f : 1.f);
+    }
+    // z of output item k of row oy (EPI), or the out-of-range offset
+    auto zload = [&](int k, int oy, bool on) {
+        if constexpr (EPI != EPI_NONE) {
+            const int v = tid + k * NT;
+            const int ox = v / G, g = v - ox * G;
+            const long o = (((long)n * Hout + oy) * Wout + ox) * q8.ld + q8.off + c0 + g * 8;
+            zpre[k] = __builtin_bit_cast(
+                uint4, __builtin_amdgcn_raw_buffer_load_b128(qr, on && v < OG ? (int)(o * 2) : (int)IRGAN_OOB, 0, 0));
+        }
+    };
     // this thread's input items (col, group) and their offsets within an input row
     int icol[IPT], ig[IPT];
 #pragma unroll
@@ -343,8 +397,13 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
         }
     };
     issue(oy0);
+    if constexpr (EPI != EPI_NONE) {
+#pragma unroll
+        for (int k = 0; k < OPT; ++k) zload(k, oy0, true);
+    }
     __syncthreads();  // the horizontal tables
-    const float qs = Q8 ? *q8.q : 1.f;
+    float qs = 1.f;
+    if constexpr (Q8) qs = *q8.q;
     float amx = 0.f;
     int buf = 0;
 #pragma unroll 1
@@ -410,6 +469,27 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
             u.z = pk_bf16(acc[4], acc[5]);
             u.w = pk_bf16(acc[6], acc[7]);
             const long o = (((long)n * Hout + oy) * Wout + ox) * ldo + offo + c0 + g * 8;
+            if constexpr (EPI != EPI_NONE) {
+                const uint32_t wd[4] = {u.x, u.y, u.z, u.w};
+                const uint32_t zd[4] = {zpre[k].x, zpre[k].y, zpre[k].z, zpre[k].w};
+                float dv[8];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float v0 = __uint_as_float(wd[q] << 16), v1 = __uint_as_float(wd[q] & 0xffff0000u);
+                    const float x0 = (__uint_as_float(zd[q] << 16) - em[2 * q]) * er[2 * q];
+                    const float x1 = (__uint_as_float(zd[q] & 0xffff0000u) - em[2 * q + 1]) * er[2 * q + 1];
+                    const float f0 = x0 > 0.f ? 1.f : eneg, f1 = x1 > 0.f ? 1.f : eneg;
+                    dv[2 * q] = er[2 * q] * __builtin_fmaf(-x0, egx[2 * q], __builtin_fmaf(v0, f0, -eg[2 * q]));
+                    dv[2 * q + 1] =
+                        er[2 * q + 1] * __builtin_fmaf(-x1, egx[2 * q + 1], __builtin_fmaf(v1, f1, -eg[2 * q + 1]));
+                }
+                u.x = pk_bf16(dv[0], dv[1]);
+                u.y = pk_bf16(dv[2], dv[3]);
+                u.z = pk_bf16(dv[4], dv[5]);
+                u.w = pk_bf16(dv[6], dv[7]);
+                zload(k, oy + 1, oy + 1 < oy1);   // the next row's z into the registers just read
+                __builtin_amdgcn_sched_barrier(0);   // one item's temporaries at a time (register budget)
+            }
             __builtin_amdgcn_raw_buffer_store_b128(u, yr, okv ? (int)(o * 2) : (int)IRGAN_OOB, 0, 0);
             if constexpr (Q8) {
                 const uint32_t wd[4] = {u.x, u.y, u.z, u.w};
@@ -435,14 +515,18 @@ __global__ __launch_bounds__(512) void sep_pipe_kernel(const bf16_t* __restrict_
     if constexpr (Q8 && AMAX) fp8_block_amax(amx, q8.amax, blockIdx.x);
 }
 
-// the pipelined form for a (bf16 -> bf16, no accumulate) resample, or false (nothing launched)
+// the pipelined form for a (bf16 -> bf16, no accumulate) resample, or false (nothing launched);
+// epi: the EPI_APPLY instance (at most 2 taps per axis), dry: the answer alone, nothing launched
 bool sep_pipe_launch(const void* in, int in_dtype, int N, int Hin, int Win, int C, int ldi, int offi, void* out,
                      int out_dtype, int Hout, int Wout, int ldo, int offo, const int* ty, const float* wy, int Ty,
                      const int* tx, const float* wx, int Tx, const float* mr, int act, const ResQ8* q8,
-                     hipStream_t st) {
+                     hipStream_t st, const ResEpi* epi = nullptr, bool dry = false) {
     static const bool off = getenv("IRGAN_SEP_ROWS1") != nullptr;   // A/B: sep_lds_kernel
     if (off || in_dtype != IRGAN_BF16 || out_dtype != IRGAN_BF16) return false;
     const int TM = Ty > Tx ? Ty : Tx;
+    if (epi && (!mr || q8 || TM > 2 || epi->ld % 8 || epi->off % 8 ||
+                (long)N * Hout * Wout * epi->ld * 2 >= (1L << 31)))
+        return false;
     if (TM > 8 || C % 8 || ldi % 8 || offi % 8 || ldo % 8 || offo % 8) return false;
     if (q8 && (q8->ld % 8 || q8->off % 8)) return false;
     int CB = 0;
@@ -469,6 +553,22 @@ bool sep_pipe_launch(const void* in, int in_dtype, int N, int Hin, int Win, int 
     const dim3 g(N * irgan_cdiv(Hout, R) * (C / CB));
     const ResQ8 qq = q8 ? *q8 : ResQ8{};
     const int swz = sep_swz();
+    if (dry) return true;
+    if (epi) {
+        const ResEpi ee = *epi;
+#define SPE(IP, OP)                                                                                       \
+    sep_pipe_kernel<2, false, false, IP, OP, true, EPI_APPLY><<<g, 512, sh, st>>>(                        \
+        (const bf16_t*)in, Hin, Win, ldi, offi, (bf16_t*)out, Hout, Wout, ldo, offo, ty, wy, Ty, tx, wx, Tx, \
+        CB, CBP, R, mr, C, act, swz, ee)
+#define SPEO(IP)                        \
+    if (opt == 1) SPE(IP, 1);           \
+    else if (opt == 2) SPE(IP, 2);      \
+    else SPE(IP, 4);
+        if (ipt == 1) { SPEO(1) } else { SPEO(2) }
+#undef SPEO
+#undef SPE
+        return true;
+    }
 #define SPK(TMV, NORMV, Q8V, IP, OP)                                                                     \
     sep_pipe_kernel<TMV, NORMV, (Q8V) != 0, IP, OP, (Q8V) != 2><<<g, 512, sh, st>>>(                       \
         (const bf16_t*)in, Hin, Win, ldi, offi, (bf16_t*)out, Hout, Wout, ldo, offo, ty, wy, Ty, tx, wx, Tx, \
@@ -1017,6 +1117,72 @@ extern "C" int irgan_sep_resample_fp8(const void* in, int32_t in_dtype, int32_t 
 #undef SEPQ
     IRGAN_LAUNCH_CHECK();
     return 0;
+}
+
+// The InstanceNorm backward of z taken from the resample launch that makes its incoming gradient:
+// da = bf16((Wy (x) Wx) dy) is never stored.  The reduce is norm.hip's row pass that forms da per
+// pixel (rows8_adjoint_reduce_kernel), the apply sep_pipe_kernel's EPI instance; both go through
+// the same checks, so what the reduce accepts the apply accepts, and red and dz are bit for bit
+// those of irgan_sep_resample + irgan_in_bwd_reduce + irgan_in_bwd_apply.
+int in_bwd_reduce_adjoint_launch(const void* dy, int lddy, int dyoff, int Hin, int Win, const int* ty, const float* wy,
+                                 int Ty, const int* tx, const float* wx, int Tx, const void* z, int ldz, int zoff,
+                                 int act, int N, int Hout, int Wout, int C, const float* mr, double* work, float* red,
+                                 hipStream_t st);   // norm.hip
+namespace {
+// channels [o0, o0 + C) of rows of l0 elements at p0 against the same of p1: false only when no
+// byte is shared (one tensor's disjoint channel slices, or disjoint ranges)
+bool slices_alias(const void* p0, int l0, int o0, const void* p1, int l1, int o1, int C, long P) {
+    if (p0 == p1 && l0 == l1) return o0 < o1 + C && o1 < o0 + C;
+    const char *a = (const char*)p0, *b = (const char*)p1;
+    return a < b + P * l1 * 2 && b < a + P * l0 * 2;
+}
+// apply: dz given, the EPI launch; reduce: dz NULL, the row pass + finalize
+int sep_in_bwd(const void* dy, int dtype, int N, int Hin, int Win, int C, int ldi, int offi, int Hout, int Wout,
+               const int* ty, const float* wy, int Ty, const int* tx, const float* wx, int Tx, const void* z,
+               int z_dtype, int ldz, int offz, const float* mr, int act, double* work, float* red, void* dz,
+               int dz_dtype, int lddz, int offdz, hipStream_t st) {
+    if (!dy || !z || !mr || !red || !ty || !wy || !tx || !wx || Ty < 1 || Tx < 1 || (!work && !dz) ||
+        act < IRGAN_ACT_NONE || act > IRGAN_ACT_LRELU)
+        return IRGAN_EINVAL;
+    if (dtype != IRGAN_BF16 || z_dtype != IRGAN_BF16 || (dz && dz_dtype != IRGAN_BF16)) return IRGAN_EUNSUPPORTED;
+    if (getenv("IRGAN_NO_SEP_LDS")) return IRGAN_EUNSUPPORTED;
+    if ((long)N * Hout * Wout * C <= 0) return 0;
+    if (dz && slices_alias(z, ldz, offz, dz, lddz, offdz, C, (long)N * Hout * Wout)) return IRGAN_EUNSUPPORTED;
+    const ResEpi e{(const bf16_t*)z, ldz, offz, red};
+    // the reduce asks what the apply's launch would take (z's slice standing in for dz's)
+    if (!sep_pipe_launch(dy, dtype, N, Hin, Win, C, ldi, offi, dz ? dz : (void*)z, IRGAN_BF16, Hout, Wout,
+                         dz ? lddz : ldz, dz ? offdz : offz, ty, wy, Ty, tx, wx, Tx, mr, act, nullptr, st, &e, !dz))
+        return IRGAN_EUNSUPPORTED;
+    if (!dz)
+        return in_bwd_reduce_adjoint_launch(dy, ldi, offi, Hin, Win, ty, wy, Ty, tx, wx, Tx, z, ldz, offz, act, N, Hout,
+                                            Wout, C, mr, work, red, st);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace
+
+extern "C" int irgan_sep_resample_in_bwd_reduce(const void* dy, int32_t dy_dtype, int32_t N, int32_t Hin, int32_t Win,
+                                                int32_t C, int32_t lddy, int32_t dyoff, int32_t Hout, int32_t Wout,
+                                                const int32_t* ty, const float* wy, int32_t Ty, const int32_t* tx,
+                                                const float* wx, int32_t Tx, const void* z, int32_t z_dtype,
+                                                int32_t ldz, int32_t zoff, const float* mr, int32_t act, double* work,
+                                                float* red, irgan_stream_t s) {
+    if (!work) return IRGAN_EINVAL;
+    return sep_in_bwd(dy, dy_dtype, N, Hin, Win, C, lddy, dyoff, Hout, Wout, ty, wy, Ty, tx, wx, Tx, z, z_dtype, ldz,
+                      zoff, mr, act, work, red, nullptr, IRGAN_BF16, 0, 0, (hipStream_t)s);
+}
+
+extern "C" int irgan_sep_resample_in_bwd_apply(const void* dy, int32_t dy_dtype, int32_t N, int32_t Hin, int32_t Win,
+                                               int32_t C, int32_t lddy, int32_t dyoff, int32_t Hout, int32_t Wout,
+                                               const int32_t* ty, const float* wy, int32_t Ty, const int32_t* tx,
+                                               const float* wx, int32_t Tx, const void* z, int32_t z_dtype,
+                                               int32_t ldz, int32_t zoff, const float* mr, int32_t act,
+                                               const float* red, void* dz, int32_t dz_dtype, int32_t lddz,
+                                               int32_t dzoff, float* db, void* dz8, irgan_stream_t s) {
+    if (!dz) return IRGAN_EINVAL;
+    if (db || dz8) return IRGAN_EUNSUPPORTED;   // a bias gradient / an e4m3 copy: the three launches
+    return sep_in_bwd(dy, dy_dtype, N, Hin, Win, C, lddy, dyoff, Hout, Wout, ty, wy, Ty, tx, wx, Tx, z, z_dtype, ldz,
+                      zoff, mr, act, nullptr, (float*)red, dz, dz_dtype, lddz, dzoff, (hipStream_t)s);
 }
 
 extern "C" int irgan_reflect_ring_fold(const float* rows, const float* cols, int32_t nsplit, int32_t N, int32_t H,

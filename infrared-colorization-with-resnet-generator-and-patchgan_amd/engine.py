@@ -485,6 +485,24 @@ class INLayer:
         if q8 is not None:
             q8.finish(dx)
 
+    def _resample_bwd_plain(self, bufs, name, dy_small, z, act, dz, plain, db=None, q8=None):
+        """``plain(dy_small, dz)`` writes the resampled gradient, bwd() turns it into dz in place."""
+        plain(dy_small, dz)
+        self.bwd(bufs, name, dz, z, act, dz, db=db, q8=q8)
+
+    def resample_bwd(self, bufs: Buffers, name: str, dy_small: Feat, z: Feat, act, dz: Feat, fused, plain, db=None,
+                     q8=None):
+        """Backward of resample_fwd() from the resample's output gradient ``dy_small`` to dz:
+        ``fused(dy_small, z, act, mr, work, red, dz)`` where it takes the call (the resample's
+        adjoint with the IN backward on its output, ops.blur_down_bwd_in), else
+        ``plain(dy_small, dz)`` + bwd().  A bias-gradient sum and an e4m3 copy keep the plain path."""
+        want_db = db is not None and INLayer.sum_bias_grad
+        if ops.RESAMPLE_BWD_FUSED[0] and q8 is None and not want_db:
+            N, C = z.N, z.C
+            if fused(dy_small, z, act, bufs.d["mr_" + name], self._work(bufs, N, C), self._red(bufs, N, C), dz):
+                return
+        self._resample_bwd_plain(bufs, name, dy_small, z, act, dz, plain, db=db, q8=q8)
+
 class NoNorm(INLayer):
     """norm='none' (ir:162-163: ``lambda num_features: Identity()``): the layer is just its
     activation, y = act(z) [+ res], and the conv in front has no bias (use_bias is False,
@@ -524,6 +542,9 @@ class NoNorm(INLayer):
             ops.act_bwd(dy, z, act, dx)            # z > 0 <=> act(z) > 0 for ReLU / LeakyReLU
         if db is not None:
             ops.channel_sum(dx, db)
+
+    def resample_bwd(self, bufs, name, dy_small, z, act, dz, fused, plain, db=None, q8=None):
+        self._resample_bwd_plain(bufs, name, dy_small, z, act, dz, plain, db=db, q8=q8)
 
 class BNSync:
     """The SyncBN handle of BNLayer: the process group whose ranks share BatchNorm statistics
@@ -663,6 +684,9 @@ class BNLayer(INLayer):
         ops.bn_backward(dy, z, act, bufs.d["mr_" + name], self.gamma, self.beta, work, red, dx,
                         dgamma=self.dgamma if wgrad else None, dbeta=self.dbeta if wgrad else None, groups=groups,
                         eval_mode=not training, dy2=dy2)
+
+    def resample_bwd(self, bufs, name, dy_small, z, act, dz, fused, plain, db=None, q8=None):
+        self._resample_bwd_plain(bufs, name, dy_small, z, act, dz, plain, db=db, q8=q8)
 
 
 def make_norm(norm: str, store: "ParamStore" = None, key: str = None) -> INLayer:
@@ -805,17 +829,21 @@ class GenConv:
         self.norm.resample_fwd(g, self.name, self.pc, x, z, a_name, act, y, fused, plain, conv8=self._conv8(st))
 
     def bwd(self, g: Buffers, st, dy: Feat, z: Feat, act, dz: Feat, x: Feat, dx: Feat, accumulate=False, padbuf=None,
-            pend: list = None):
+            pend: list = None, resample=None):
         """Backward of fwd(): dz = the norm's backward of dy (in place when dz is dy), the weight
         gradient from x and dz, dx (+)= backward-data of dz.  The bf16 ResnetBlock convs launch
         the backward-data first, every other case the weight gradient.  ``pend`` (the ResnetBlock
         convs off the e4m3 path): the weight gradient is not launched but appended to it as
         (layer, x, dz) -- the caller launches several at once (wgrad_flush) and keeps x and dz
-        unchanged until then."""
+        unchanged until then.  ``resample`` = (fused, plain): the backward of resample_fwd() --
+        dy is the gradient of the resample's output (INLayer.resample_bwd)."""
         e, on = self.eng, st.on[self.group]
         dz8 = Feat(g.get(self.dy8, (*dz.t.shape[:3], dz.C), torch.float8_e4m3fn)) if on else None
-        self.norm.bwd(g, self.name, dy, z, act, dz, db=e._bgrad(self.key + ".bias"),
-                      q8=ops.Fp8Out(e.f8a, self.rec.s_dy, dz8) if on else None)
+        db, q8 = e._bgrad(self.key + ".bias"), ops.Fp8Out(e.f8a, self.rec.s_dy, dz8) if on else None
+        if resample is not None:
+            self.norm.resample_bwd(g, self.name, dy, z, act, dz, *resample, db=db, q8=q8)
+        else:
+            self.norm.bwd(g, self.name, dy, z, act, dz, db=db, q8=q8)
         if on:
             self._wgrad(st, x, dz, dz8)
             if self.s_calib is not None:
@@ -1252,14 +1280,14 @@ class GeneratorEngine:
             flush(True)
         self._fp8_roll(st, "res", "dy")   # next step's backward-data scales
         # down2 (+ blur-down)
-        if self.no_aa:
-            dz2 = dh
-        else:
-            dz2 = Feat(g.get("da2", (B, H1, W1, c2), T))
-            ops.blur_down_bwd(dh, dz2)
         dx1 = dcat1.sl(c2, c1)
         # (accumulated: x1 feeds down2 and the up1 concat)
-        self.c_down2.bwd(g, st, dz2, Feat(g.d["z2"]), ACT_RELU, dz2, x1, dx1, accumulate=True)
+        if self.no_aa:
+            self.c_down2.bwd(g, st, dh, Feat(g.d["z2"]), ACT_RELU, dh, x1, dx1, accumulate=True)
+        else:
+            dz2 = Feat(g.get("da2", (B, H1, W1, c2), T))
+            self.c_down2.bwd(g, st, dh, Feat(g.d["z2"]), ACT_RELU, dz2, x1, dx1, accumulate=True,
+                             resample=(ops.blur_down_bwd_in, ops.blur_down_bwd))
         self._fp8_roll(st, "ud", "ud_dy")   # next step's scales of the two dY slots
         # down1 (+ blur-down)
         z1 = Feat(g.d["z1"])
@@ -1268,8 +1296,8 @@ class GeneratorEngine:
             self.norms["down1"].bwd(g, "down1", dx1, z1, ACT_RELU, dz1, db=self._bgrad("down1.0.bias"))
         else:
             dz1 = Feat(g.get("da1", (B, H, W, c1), T))
-            ops.blur_down_bwd(dx1, dz1)
-            self.norms["down1"].bwd(g, "down1", dz1, z1, ACT_RELU, dz1, db=self._bgrad("down1.0.bias"))
+            self.norms["down1"].resample_bwd(g, "down1", dx1, z1, ACT_RELU, dz1, ops.blur_down_bwd_in,
+                                             ops.blur_down_bwd, db=self._bgrad("down1.0.bias"))
         wg(self.down1, "down1.0", x0, dz1)
         dx0 = dcat2.sl(c1, c0)
         ops.conv_dgrad(self.down1, dz1, dx0, accumulate=True)

@@ -998,6 +998,55 @@ def blur_down_bwd(dy: Feat, dx: Feat, accumulate=False):
                  accumulate)
 
 
+# The InstanceNorm backward of down1 / down2 taken from the Downsample adjoint without storing
+# the up-sampled gradient (blur_down_bwd_in); IRGAN_RESAMPLE_BWD_FUSED=0: the adjoint launch
+# followed by reduce + finalize + apply (the A/B switch)
+RESAMPLE_BWD_FUSED = [os.environ.get("IRGAN_RESAMPLE_BWD_FUSED") != "0"]
+
+
+def set_resample_bwd_fused(on: bool) -> bool:
+    """blur_down_bwd_in (default) or blur_down_bwd + in_backward for the layers that can take
+    either (INLayer.resample_bwd).  Returns the previous setting."""
+    old, RESAMPLE_BWD_FUSED[0] = RESAMPLE_BWD_FUSED[0], bool(on)
+    return old
+
+
+def _shares_bytes(a: Feat, b: Feat) -> bool:
+    """False only when the two slices share no byte: disjoint channels of one tensor, or
+    disjoint storage ranges."""
+    if a.t.data_ptr() == b.t.data_ptr() and a.ld == b.ld:
+        return a.off < b.off + b.C and b.off < a.off + a.C
+    a0, b0 = a.t.data_ptr(), b.t.data_ptr()
+    return a0 < b0 + b.t.numel() * b.t.element_size() and b0 < a0 + a.t.numel() * a.t.element_size()
+
+
+def sep_resample_in_bwd(dy: Feat, ytab, xtab, z: Feat, act, mr, work, red, dz: Feat) -> bool:
+    """dz = backward of act(InstanceNorm(z)) applied to resample(dy), the resampled gradient
+    never stored (irgan_sep_resample_in_bwd_reduce + _apply; red is an output).  False when the
+    library does not take the arguments -- then NOTHING ran and nothing was written."""
+    (ty, wy, ry, Ty), (tx, wx, rx, Tx) = ytab, xtab
+    assert (ry, rx) == (z.H, z.W) == (dz.H, dz.W) and dy.C == z.C == dz.C and dy.N == z.N == dz.N, \
+        "sep_resample_in_bwd shape mismatch"
+    if dz.dt != BF16 or dz.ld % 8 or dz.off % 8 or _shares_bytes(z, dz):
+        return False   # what the apply refuses, asked before the reduce runs
+    head = (dy.ptr, dy.dt, dy.N, dy.H, dy.W, dy.C, dy.ld, dy.off, z.H, z.W, P(ty), P(wy), Ty, P(tx), P(wx), Tx,
+            z.ptr, z.dt, z.ld, z.off, P(mr), act)
+    if not _timed("resample_in_bwd_reduce", z,
+                  lambda: _try("irgan_sep_resample_in_bwd_reduce", *head, P(work), P(red), stream())):
+        return False
+    _timed("resample_in_bwd_apply", z,
+           lambda: _lib.call("irgan_sep_resample_in_bwd_apply", *head, P(red), dz.ptr, dz.dt, dz.ld, dz.off, None,
+                             None, stream()))
+    return True
+
+
+def blur_down_bwd_in(dy: Feat, z: Feat, act, mr, work, red, dz: Feat) -> bool:
+    """The backward of Downsample(act(IN(z))) down to z's gradient: blur_down_bwd + in_backward
+    without the full-resolution gradient in between (sep_resample_in_bwd)."""
+    return sep_resample_in_bwd(dy, resample_table(RS_DOWN, z.H, transpose=True),
+                               resample_table(RS_DOWN, z.W, transpose=True), z, act, mr, work, red, dz)
+
+
 def _up_axis(n_in, n_out, transpose):
     if n_out == 2 * n_in:
         return resample_table(RS_UP, n_in, transpose=transpose)
