@@ -569,6 +569,20 @@ IRGAN_API int irgan_act_bwd(const void* dy, int32_t dy_dtype, int32_t lddy, int3
  * loss accumulated into *loss (fp64). */
 IRGAN_API int irgan_hinge(const float* pred, int32_t n_half, int32_t mode, float scale, float* grad,
                 double* loss, irgan_stream_t s);
+/* The GAN objective of the step on the same patch logits (Config.gan_mode), loss value and
+ * gradient in one pass.  side 0: pred = [real (n_half); fake (n_half)], D's loss; side 1:
+ * pred = fake (n_half), G's GAN term.  t = real_label, means over the n_half logits of a half:
+ *   objective 0 (hinge):   irgan_hinge(pred, n_half, side, scale, ...) itself, the same launch
+ *   objective 1 (LSGAN):   side 0: 0.5*(mean (r-t)^2 + mean f^2)        side 1: mean (f-1)^2
+ *   objective 2 (vanilla): side 0: 0.5*(mean bce(r,t) + mean bce(f,0))  side 1: mean bce(f,1)
+ * with bce(x,y) = max(x,0) - x*y + log1p(exp(-|x|)) (binary_cross_entropy_with_logits; its
+ * gradient is sigmoid(x) - y; finite for every finite x).  *loss += scale*value (fp64), grad =
+ * scale * d value / d pred, written.  t smooths D's real target only (one-sided); G's target is 1.
+ * IRGAN_EINVAL: side not 0 / 1, objective not 0..2, real_label not finite or outside (0, 1],
+ * objective 0 with real_label != 1.  n_half <= 0: as irgan_hinge (nothing is read or written
+ * but the loss word). */
+IRGAN_API int irgan_gan_loss(const float* pred, int32_t n_half, int32_t side, int32_t objective, float real_label,
+                   float scale, float* grad, double* loss, irgan_stream_t s);
 /* Pixel / feature L1: loss += w*mean|a-b|; ga = w*sign(a-b)/cnt (dtype of ga). */
 IRGAN_API int irgan_l1(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* ga,
              int32_t ga_dtype, int32_t accumulate, double* loss, irgan_stream_t s);

@@ -56,6 +56,44 @@ __global__ __launch_bounds__(TPB) void hinge_kernel(const float* __restrict__ pr
     block_add(loss, mode == 0 ? 0.5f * acc * inv * scale : -acc * inv * scale);
 }
 
+// The LSGAN and BCE ("vanilla") objectives on the same patch logits, with hinge_kernel's layout
+// and sides.  Per element the target y and the weight c of its mean are
+//   side 0, pred = [real (n) ; fake (n)]:  y = t (the smoothed real label) | 0,  c = 0.5
+//   side 1, pred = fake (n):               y = 1,                            c = 1
+// and   LSGAN: term (p - y)^2,                                   d term / d p = 2 (p - y)
+//       BCE:   term max(p, 0) - p y + log1p(exp(-|p|)),          d term / d p = sigmoid(p) - y
+// loss += scale * c * mean(term), grad = scale * c / n * d term / d p (written, not accumulated).
+// exp(-|p|) <= 1 never overflows, so the BCE arm is finite for any finite logit.  The gradient's
+// few operations after expf run in fp64 and round once: sigmoid(p) - 1 cancels, and the tensor is
+// 2*B*30*30 logits, so the extra width costs nothing that shows in a step.
+constexpr int GAN_LSGAN = 1, GAN_BCE = 2;
+
+template <int OBJ>
+__global__ __launch_bounds__(TPB) void gan_loss_kernel(const float* __restrict__ pred, int n, int side, float t,
+                                                       float scale, float* __restrict__ grad,
+                                                       double* __restrict__ loss) {
+    const long total = side == 0 ? 2L * n : n;
+    const float c = side == 0 ? 0.5f : 1.f;
+    const double k = (double)c * (double)scale / (double)n;
+    float acc = 0.f;
+    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
+        const float p = pred[i];
+        const float y = side == 0 ? (i < n ? t : 0.f) : 1.f;
+        if constexpr (OBJ == GAN_LSGAN) {
+            const float d = p - y;
+            acc += d * d;
+            grad[i] = (float)(2.0 * k * ((double)p - (double)y));
+        } else {
+            const float e = expf(-fabsf(p));
+            acc += fmaxf(p, 0.f) - p * y + log1pf(e);
+            const double ed = (double)e;
+            const double sg = (p >= 0.f ? 1.0 : ed) / (1.0 + ed);
+            grad[i] = (float)(k * (sg - (double)y));
+        }
+    }
+    block_add(loss, c * acc * (1.f / (float)n) * scale);
+}
+
 template <typename T>
 IRGAN_HD void ld8t(const T* p, long i, float* o) {
     if constexpr (sizeof(T) == 2) {
@@ -590,6 +628,26 @@ extern "C" int irgan_hinge(const float* pred, int32_t n_half, int32_t mode, floa
     if (mode != 0 && mode != 1) return IRGAN_EINVAL;
     long total = mode == 0 ? 2L * n_half : n_half;
     hinge_kernel<<<nblocks_red(total), TPB, 0, (hipStream_t)s>>>(pred, n_half, mode, scale, grad, loss);
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// objective 0 is irgan_hinge's launch itself (the default step's kernel and arguments are unchanged)
+extern "C" int irgan_gan_loss(const float* pred, int32_t n_half, int32_t side, int32_t objective, float real_label,
+                              float scale, float* grad, double* loss, irgan_stream_t s) {
+    if (side != 0 && side != 1) return IRGAN_EINVAL;
+    if (objective != 0 && objective != GAN_LSGAN && objective != GAN_BCE) return IRGAN_EINVAL;
+    if (!(real_label > 0.f && real_label <= 1.f)) return IRGAN_EINVAL;   // NaN and inf fail it too
+    if (objective == 0 && real_label != 1.f) return IRGAN_EINVAL;
+    const long total = side == 0 ? 2L * n_half : n_half;
+    const int nb = nblocks_red(total);
+    hipStream_t st = (hipStream_t)s;
+    if (objective == 0)
+        hinge_kernel<<<nb, TPB, 0, st>>>(pred, n_half, side, scale, grad, loss);
+    else if (objective == GAN_LSGAN)
+        gan_loss_kernel<GAN_LSGAN><<<nb, TPB, 0, st>>>(pred, n_half, side, real_label, scale, grad, loss);
+    else
+        gan_loss_kernel<GAN_BCE><<<nb, TPB, 0, st>>>(pred, n_half, side, real_label, scale, grad, loss);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -3,9 +3,9 @@
 One ``GANStep.step(ir, rgb)`` = the reference's inner-loop body
 (ir:1636-1681) in its minimal form: one G forward reused (detached) for the D
 step; D forward/backward on the batched [real; fake] pair; D Adam; D forward on
-fake with the updated D; hinge + L1 + VGG-perceptual + TV + SSIM losses with
-their gradients written directly; G backward; G Adam.  No autograd tape: every
-backward is an explicit HIP kernel sequence over activations kept in static
+fake with the updated D; GAN (hinge, or Config.gan_mode's LSGAN / BCE) + L1 +
+VGG-perceptual + TV + SSIM losses with their gradients written directly; G
+backward; G Adam.  No autograd tape: every backward is an explicit HIP kernel sequence over activations kept in static
 NHWC buffers (capturable in a HIP graph).
 
 Parameters live in flat fp32 buffers (one per network) whose per-key slices are
@@ -1699,6 +1699,12 @@ class GANStep:
         # the plain path: no reduction, no extra launch, the slot stays 0
         self.clip_G = float(getattr(cfg, "clip_grad_G", 0.0) or 0.0)
         self.clip_D = float(getattr(cfg, "clip_grad_D", 0.0) or 0.0)
+        # Config.gan_mode / gan_real_label: the objective of both GAN terms (ops.gan_loss: "hinge",
+        # the reference's, is ops.hinge's own launch; "lsgan", "vanilla") and D's real target
+        self.gan_mode = getattr(cfg, "gan_mode", "hinge") or "hinge"
+        self.gan_real_label = float(getattr(cfg, "gan_real_label", 1.0))
+        if self.gan_mode not in ops.GAN_MODES:
+            raise ValueError(f"gan_mode must be one of {sorted(ops.GAN_MODES)}, got {self.gan_mode!r}")
         # the D step (D forward/backward on [real; fake] and its all-reduce) runs on a
         # side stream, concurrently with the G-step terms that do not read D (L1,
         # VGG, TV, SSIM); IRGAN_NO_D_OVERLAP=1 keeps everything on one stream
@@ -1808,7 +1814,7 @@ class GANStep:
             # BatchNorm: netD(real), netD(fake) statistics (under SyncBN each group over all ranks)
             pred = self.dis.forward(din, tag="d", groups=2, bn_sync=True)
             dpred = b.get("dpred", tuple(pred.shape), torch.float32)
-            ops.hinge(pred, pred[:B].numel(), 0, 1.0, dpred, L[0:1])
+            ops.gan_loss(pred, pred[:B].numel(), 0, self.gan_mode, self.gan_real_label, 1.0, dpred, L[0:1])
             # D grads reduced tail-first under the D backward (8 MB buckets: model.8 + the head
             # go out while model.5 / .2 / .0 still run), each bucket's Adam right behind it
             # (the weight gradients on the main stream instead, beside this chain: -1.4 %, the main
@@ -1826,7 +1832,7 @@ class GANStep:
                 ops.axpby(Feat(fake), 1.0, Feat(din.t[B:], cin, cout))
             predg = self.dis.forward(din.batch(B, B), tag="g", bn_sync=True)
             dpg = b.get("dpredg", tuple(predg.shape), torch.float32)
-            ops.hinge(predg, predg.numel(), 1, cfg.lambda_gan, dpg, L[1:2])
+            ops.gan_loss(predg, predg.numel(), 1, self.gan_mode, self.gan_real_label, cfg.lambda_gan, dpg, L[1:2])
             dd = self.dis.backward(dpg, want_wgrad=False, want_dinput=True, tag="g")
             _mark(ph, "dend", self.side)
         if not terms_first:

@@ -7,6 +7,8 @@ path and the pieces a train/test driver touches:
     (ir:168-209), get_lr_lambda (ir:212), get_filter (ir:240),
     ResnetUNetGenerator (ir:425), NLayerDiscriminator (ir:576),
     VGGPerceptual (ir:642), tv_loss (ir:686), ssim_loss_torch (ir:714),
+    gan_loss_D / gan_loss_G (the step's GAN objective, Config.gan_mode: ir:1647-1662 and
+    the LSGAN / BCE forms),
     IRColorizationModel (ir:757), validate_kaist (ir:1521), train_kaist (ir:1549),
     and the test-mode names re-exported from inference.py / evaluation.py:
     ir_to_tensor, tensor_to_rgb_image, compute_metrics, save_best_k_outputs,
@@ -39,6 +41,7 @@ from .ops import BF16, F32, Feat
 
 __all__ = ["Config", "Identity", "get_norm_layer", "init_weights", "init_net", "get_lr_lambda", "get_filter",
            "ResnetUNetGenerator", "NLayerDiscriminator", "VGGPerceptual", "tv_loss", "ssim_loss_torch",
+           "gan_loss_D", "gan_loss_G",
            "IRColorizationModel", "GANTrainer", "validate_kaist", "train_kaist", "SyntheticPairDataset",
            "g_param_shapes", "d_param_shapes", "vgg_param_shapes", "seeded_state", "dp_loaders", "val_shard",
            "compute_metrics", "save_best_k_outputs", "run_test", "make_comparison_collage", "save_comparison_image",
@@ -112,6 +115,10 @@ class Config:
         self.clip_grad_G = 0.0           # > 0: clip G's / D's gradient to this global L2 norm inside the fused
         self.clip_grad_D = 0.0           # Adam launch (torch.nn.utils.clip_grad_norm_ semantics) and report the
                                          # norm as grad_norm_G / grad_norm_D in GANTrainer.losses; 0 = off
+        self.gan_mode = "hinge"          # the GAN objective of the fused step: "hinge" (the reference's, ir:1647-
+                                         # 1662), "lsgan" (least squares) or "vanilla" (BCE with logits)
+        self.gan_real_label = 1.0        # D's target for real patches, in (0, 1]: < 1 is one-sided label
+                                         # smoothing (lsgan / vanilla only; G's target stays 1)
 
 
 # =============================================================================
@@ -622,6 +629,54 @@ def ssim_loss_torch(img1, img2, window_size=11, size_average=True):
     return _SSIMFn.apply(img1, img2, bool(size_average), int(window_size))
 
 
+class _GANLossFn(torch.autograd.Function):
+    """ops.gan_loss on the concatenated logits: one launch gives the value and the gradient,
+    backward splits the gradient and scales it by the upstream one.  The same kernel with the
+    same arguments as the fused step's, so a hand-written loop gets its gradients."""
+
+    @staticmethod
+    def forward(ctx, side, mode, real_label, *preds):
+        flat = torch.cat([p.detach().reshape(-1) for p in preds])
+        grad = torch.empty_like(flat)
+        loss = torch.zeros(1, dtype=torch.float64, device=flat.device)
+        ops.gan_loss(flat, preds[0].numel(), side, mode, real_label, 1.0, grad, loss)
+        ctx.save_for_backward(grad)
+        ctx.shapes = [p.shape for p in preds]
+        return loss.float()[0]
+
+    @staticmethod
+    def backward(ctx, gl):
+        (grad,) = ctx.saved_tensors
+        n = grad.numel() // len(ctx.shapes)
+        return (None, None, None, *[(grad[i * n:(i + 1) * n] * gl).reshape(s) for i, s in enumerate(ctx.shapes)])
+
+
+def _gan_logits(what, *preds):
+    for p in preds:
+        _require_cuda(p, what)
+        if p.dtype != torch.float32:
+            raise ValueError(f"{what}: the logits are fp32 tensors, got {p.dtype}")
+        if p.numel() != preds[0].numel() or p.numel() == 0:
+            raise ValueError(f"{what}: real and fake logits must have one non-zero element count, got "
+                             f"{[tuple(q.shape) for q in preds]}")
+
+
+def gan_loss_D(pred_real, pred_fake, mode="hinge", real_label=1.0):
+    """D's loss of Config.gan_mode ``mode`` on netD's patch logits, on the fused step's kernel:
+    "hinge" 0.5*(mean relu(1-r) + mean relu(1+f)) (ir:1647-1649), "lsgan" 0.5*(mean (r-t)^2 +
+    mean f^2), "vanilla" 0.5*(mean bce(r,t) + mean bce(f,0)); t = ``real_label`` in (0, 1]
+    (one-sided label smoothing; 1 under "hinge").  A scalar with autograd to both inputs."""
+    _gan_logits("gan_loss_D", pred_real, pred_fake)
+    return _GANLossFn.apply(0, mode, float(real_label), pred_real, pred_fake)
+
+
+def gan_loss_G(pred_fake, mode="hinge"):
+    """G's GAN term (before lambda_gan) on netD(fake)'s patch logits, on the fused step's
+    kernel: "hinge" -mean f (ir:1662), "lsgan" mean (f-1)^2, "vanilla" mean bce(f,1)."""
+    _gan_logits("gan_loss_G", pred_fake)
+    return _GANLossFn.apply(1, mode, 1.0, pred_fake)
+
+
 # =============================================================================
 # 7) Model wrapper (ir:757-796)
 # =============================================================================
@@ -703,6 +758,22 @@ def _check_clip_grad(cfg):
     return tuple(out)
 
 
+def _check_gan(cfg):
+    """(Config.gan_mode, Config.gan_real_label); ValueError for a mode ops.GAN_MODES does not
+    name, a label that is not finite or lies outside (0, 1], and a smoothed label under
+    "hinge" (its margins are not targets: there is nothing to smooth)."""
+    mode = getattr(cfg, "gan_mode", "hinge")
+    if mode not in ops.GAN_MODES:
+        raise ValueError(f"gan_mode must be one of {sorted(ops.GAN_MODES)}, got {mode!r}")
+    t = float(getattr(cfg, "gan_real_label", 1.0))
+    if not (math.isfinite(t) and 0.0 < t <= 1.0):
+        raise ValueError(f"gan_real_label is D's target for real patches, finite and in (0, 1], got {t!r}")
+    if mode == "hinge" and t != 1.0:
+        raise ValueError(f"gan_real_label = {t!r} needs gan_mode 'lsgan' or 'vanilla': the hinge objective has "
+                         "no real target to smooth")
+    return mode, t
+
+
 class GANTrainer:
     """Owns G (through the model), D, VGG and both Adams; ``step(ir, rgb)`` runs
     the fused HIP train step and returns the device loss vector (no host sync)."""
@@ -715,6 +786,7 @@ class GANTrainer:
         _refuse_multi_rank_batch_norm(cfg, process_group)   # before any GPU work
         self.ema_decay = _check_ema_decay(cfg)              # likewise
         self.clip_grad_G, self.clip_grad_D = _check_clip_grad(cfg)
+        self.gan_mode, self.gan_real_label = _check_gan(cfg)
         dev = torch.device(cfg.device)
         dt = getattr(cfg, "compute_dtype", "bf16")
         if getattr(cfg, "deterministic", False):
@@ -980,6 +1052,7 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
         log(f"Initializing generator from: {cfg.init_G_weights}")
         model.load_weights(cfg.init_G_weights, log=log)
     trainer = GANTrainer(cfg, model=model)
+    log(f"GAN objective: {trainer.gan_mode} (real label {trainer.gan_real_label:g})")
     if trainer_hook is not None:
         trainer_hook(trainer)
     if rank == 0:

@@ -1171,6 +1171,20 @@ def hinge(pred: torch.Tensor, n_half: int, mode: int, scale: float, grad: torch.
     _lib.call("irgan_hinge", P(pred), n_half, mode, ctypes.c_float(scale), P(grad), P(loss), stream())
 
 
+GAN_MODES = {"hinge": 0, "lsgan": 1, "vanilla": 2}   # Config.gan_mode -> irgan_gan_loss's objective
+
+
+def gan_loss(pred: torch.Tensor, n_half: int, side: int, mode: str, real_label: float, scale: float,
+             grad: torch.Tensor, loss: torch.Tensor):
+    """The GAN objective ``mode`` (a key of GAN_MODES) on the patch logits: side 0 is D's loss on
+    [real (n_half); fake (n_half)] with the real target ``real_label``, side 1 G's term on fake
+    (n_half).  ``loss`` += scale * value, ``grad`` written.  "hinge" is ops.hinge's launch."""
+    if mode not in GAN_MODES:
+        raise ValueError(f"gan_mode must be one of {sorted(GAN_MODES)}, got {mode!r}")
+    _lib.call("irgan_gan_loss", P(pred), n_half, side, GAN_MODES[mode], ctypes.c_float(real_label),
+              ctypes.c_float(scale), P(grad), P(loss), stream())
+
+
 def l1(a: torch.Tensor, b: torch.Tensor, w: float, ga: torch.Tensor, loss: torch.Tensor, accumulate=False):
     _lib.call("irgan_l1", P(a), P(b), dt_code(a), a.numel(), ctypes.c_float(w), P(ga),
               dt_code(ga) if ga is not None else 0, int(accumulate), P(loss), stream())
