@@ -537,6 +537,16 @@ IRGAN_API int irgan_maxpool_fwd(const void* x, int32_t dtype, int32_t N, int32_t
                       void* y, irgan_stream_t s);
 IRGAN_API int irgan_maxpool_bwd(const void* x, const void* dy, int32_t dtype, int32_t N, int32_t H,
                       int32_t W, int32_t C, void* dx, int32_t relu_mask, irgan_stream_t s);
+/* irgan_maxpool_bwd with relu_mask = 1 for a pool input that is a perceptual tap
+ * (Config.perc_layers: relu1_2, relu2_2): x the fake images' pre-pool map, xr the real images',
+ * both dense NHWC [N][H][W][C] of `dtype` (dy, dx too), count = N*H*W*C:
+ *   dx[q] = (argmax == q && max > 0 ? dy : 0) + (x[q] > 0 ? sgn(x[q] - xr[q]) * w/count : 0)
+ *   *loss += w/count * sum |x - xr|   (fp64)
+ * at all four window positions, the fp32 sum rounded once: bit-identical to irgan_maxpool_bwd
+ * followed by irgan_l1_tap(accumulate = 1).  IRGAN_EUNSUPPORTED (nothing launched): odd H or W
+ * (the tap needs the row / column no window visits), N*(H/2) > 65535. */
+IRGAN_API int irgan_maxpool_bwd_tap(const void* x, const void* xr, const void* dy, int32_t dtype, int32_t N,
+                      int32_t H, int32_t W, int32_t C, void* dx, float w, double* loss, irgan_stream_t s);
 
 /* ---- layout / elementwise ---- */
 /* NCHW fp32 -> NHWC slice (dtype), optional affine y = x*scale[c] + shift[c]. */
@@ -586,6 +596,13 @@ IRGAN_API int irgan_gan_loss(const float* pred, int32_t n_half, int32_t side, in
 /* Pixel / feature L1: loss += w*mean|a-b|; ga = w*sign(a-b)/cnt (dtype of ga). */
 IRGAN_API int irgan_l1(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* ga,
              int32_t ga_dtype, int32_t accumulate, double* loss, irgan_stream_t s);
+/* One perceptual tap (Config.perc_layers): a = the fake images' post-ReLU features, b the real
+ * images' (dtype: IRGAN_F32 / IRGAN_BF16), dz the gradient w.r.t. the layer's PRE-activation
+ * (dz_dtype likewise; not NULL):  *loss += w*mean|a-b| (fp64) and, per element,
+ *   dz = (accumulate ? dz : 0) + (a > 0 ? sgn(a-b) * w/count : 0),  sgn(0) = 0,
+ * the sum formed in fp32 and rounded once.  IRGAN_EINVAL: another dtype, dz NULL. */
+IRGAN_API int irgan_l1_tap(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* dz,
+                 int32_t dz_dtype, int32_t accumulate, double* loss, irgan_stream_t s);
 /* TV (ir:686-694) on NHWC fp32 x: loss += w*tv(x), g += grad. */
 IRGAN_API int irgan_tv(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, float w, float* g,
              double* loss, irgan_stream_t s);

@@ -1,6 +1,7 @@
 """``python -m infrared-colorization-with-resnet-generator-and-patchgan_amd [train|test]
 [--img-size N | HxW | native] [--load-size N | HxW | native] [--ema-decay D] [--clip-grad-G X]
-[--clip-grad-D X] [--gan-mode hinge|lsgan|vanilla] [--gan-real-label T]`` -- the reference's script
+[--clip-grad-D X] [--gan-mode hinge|lsgan|vanilla] [--gan-real-label T] [--perc-layers L,L,...]
+[--perc-weights W,W,...]`` -- the reference's script
 entry point (ir:1730-1756) with cfg.mode taken from the command line (default: Config's "test").
 ``--img-size`` sets cfg.img_size: N for N x N, HxW (height first, e.g. 512x640) or ``native`` for
 every frame at its own size; ``--load-size`` sets cfg.load_size, the training crop jitter: every
@@ -11,8 +12,10 @@ of the generator weights); ``--clip-grad-G`` / ``--clip-grad-D`` set cfg.clip_gr
 maximal L2 norm of the generator's / discriminator's gradient (clipped inside the fused Adam update,
 the norms join the step log); ``--gan-mode`` sets cfg.gan_mode, the GAN objective of the fused step
 (``hinge``, the reference's; ``lsgan``; ``vanilla`` = BCE with logits), and ``--gan-real-label`` cfg.gan_real_label,
-D's target for real patches in (0, 1] (e.g. 0.9: one-sided label smoothing, lsgan / vanilla only).  Without a
-flag Config's value stands."""
+D's target for real patches in (0, 1] (e.g. 0.9: one-sided label smoothing, lsgan / vanilla only);
+``--perc-layers`` sets cfg.perc_layers, the VGG maps of the perceptual term (comma-separated names out of
+relu1_1 .. relu3_3, e.g. ``relu1_2,relu2_2,relu3_3``), and ``--perc-weights`` cfg.perc_weights, one weight per
+layer (e.g. ``1,0.5,0.25``).  Without a flag Config's value stands."""
 import argparse
 import sys
 
@@ -31,6 +34,10 @@ def config_from_argv(argv):
     ap.add_argument("--clip-grad-D", type=float, default=argparse.SUPPRESS, metavar="X", dest="clip_grad_D")
     ap.add_argument("--gan-mode", choices=sorted(GAN_MODES), default=argparse.SUPPRESS)
     ap.add_argument("--gan-real-label", type=float, default=argparse.SUPPRESS, metavar="T")
+    ap.add_argument("--perc-layers", type=lambda v: tuple(n.strip() for n in v.split(",")),
+                    default=argparse.SUPPRESS, metavar="L,L,...")
+    ap.add_argument("--perc-weights", type=lambda v: tuple(float(w) for w in v.split(",")),
+                    default=argparse.SUPPRESS, metavar="W,W,...")
     a = ap.parse_args(argv)
     cfg = Config()
     if a.mode is not None:
@@ -41,7 +48,7 @@ def config_from_argv(argv):
         cfg.load_size = a.load_size
     if hasattr(a, "ema_decay"):
         cfg.ema_decay = a.ema_decay
-    for name in ("clip_grad_G", "clip_grad_D", "gan_mode", "gan_real_label"):
+    for name in ("clip_grad_G", "clip_grad_D", "gan_mode", "gan_real_label", "perc_layers", "perc_weights"):
         if hasattr(a, name):
             setattr(cfg, name, getattr(a, name))
     return cfg

@@ -69,6 +69,21 @@ IRGAN_HD float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// *dst += the sum of v over the block's NT threads: fp32 per wave and per block, then ONE fp64
+// atomic (the loss kernels' reduction).  Every thread of the block must reach it.
+template <int NT>
+IRGAN_HD void block_sum_add(double* dst, float v) {
+    __shared__ float red[NT / 64];
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int i = 0; i < NT / 64; ++i) t += red[i];
+        atomicAdd(dst, (double)t);
+    }
+}
 
 // ---- LDS-DMA pipelines ---------------------------------------------------
 // global_load_lds_dwordx4: 16 bytes per lane from `src` into lds + 16*lane

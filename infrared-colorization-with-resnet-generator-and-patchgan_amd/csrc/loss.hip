@@ -8,18 +8,7 @@ namespace {
 
 constexpr int TPB = 256;
 
-IRGAN_HD void block_add(double* dst, float v) {
-    __shared__ float red[TPB / 64];
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int i = 0; i < TPB / 64; ++i) t += red[i];
-        atomicAdd(dst, (double)t);
-    }
-}
+IRGAN_HD void block_add(double* dst, float v) { block_sum_add<TPB>(dst, v); }
 
 IRGAN_HD float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
@@ -153,6 +142,41 @@ __global__ __launch_bounds__(TPB) void l1_kernel(const T* __restrict__ a, const 
                 if (accumulate) gv += to_f<G>(ga[i]);
                 ga[i] = from_f<G>(gv);
             }
+        }
+    }
+    block_add(loss, acc * inv);
+}
+
+// One perceptual tap (Config.perc_layers): a = relu(z) of the fake images, b the real images'
+// map; loss += w*mean|a-b| and the term's gradient w.r.t. the PRE-activation z lands in dz:
+//   dz = (accumulate ? dz : 0) + (a > 0 ? sgn(a-b) * w/count : 0)
+// summed in fp32 and rounded once to dz's type.  l1_kernel's two forms.
+IRGAN_HD float tap_grad(float a, float b, float inv) { return a > 0.f ? sgn(a - b) * inv : 0.f; }
+
+template <typename T, typename G, bool VEC>
+__global__ __launch_bounds__(TPB) void l1_tap_kernel(const T* __restrict__ a, const T* __restrict__ b, long count,
+                                                     float w, G* __restrict__ dz, int accumulate,
+                                                     double* __restrict__ loss) {
+    float acc = 0.f;
+    const float inv = w / (float)count;
+    if constexpr (VEC) {
+        for (long i = (blockIdx.x * (long)TPB + threadIdx.x) * 8; i < count; i += (long)gridDim.x * TPB * 8) {
+            float av[8], bv[8], gv[8];
+            ld8t<T>(a, i, av);
+            ld8t<T>(b, i, bv);
+            if (accumulate) ld8t<G>(dz, i, gv);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                acc += fabsf(av[k] - bv[k]);
+                gv[k] = (accumulate ? gv[k] : 0.f) + tap_grad(av[k], bv[k], inv);
+            }
+            st8t<G>(dz, i, gv);
+        }
+    } else {
+        for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < count; i += (long)gridDim.x * TPB) {
+            const float av = to_f<T>(a[i]), bv = to_f<T>(b[i]);
+            acc += fabsf(av - bv);
+            dz[i] = from_f<G>((accumulate ? to_f<G>(dz[i]) : 0.f) + tap_grad(av, bv, inv));
         }
     }
     block_add(loss, acc * inv);
@@ -676,6 +700,36 @@ extern "C" int irgan_l1(const void* a, const void* b, int32_t dtype, int64_t cou
         else L1_LAUNCH(bf16_t, float);
     }
 #undef L1_LAUNCH
+    IRGAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int irgan_l1_tap(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* dz,
+                            int32_t dz_dtype, int32_t accumulate, double* loss, irgan_stream_t s) {
+    hipStream_t st = (hipStream_t)s;
+    if ((dtype != IRGAN_F32 && dtype != IRGAN_BF16) || (dz_dtype != IRGAN_F32 && dz_dtype != IRGAN_BF16) || !dz)
+        return IRGAN_EINVAL;
+    if (count <= 0) return 0;
+    const bool vec = count % 8 == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) &&
+                     ((uintptr_t)dz % 16 == 0);
+    const int nb = nblocks_red(vec ? count / 8 : count);
+#define TAP_LAUNCH(T, G)                                                                                          \
+    do {                                                                                                          \
+        if (vec)                                                                                                  \
+            l1_tap_kernel<T, G, true><<<nb, TPB, 0, st>>>((const T*)a, (const T*)b, count, w, (G*)dz, accumulate, \
+                                                          loss);                                                  \
+        else                                                                                                      \
+            l1_tap_kernel<T, G, false><<<nb, TPB, 0, st>>>((const T*)a, (const T*)b, count, w, (G*)dz,            \
+                                                           accumulate, loss);                                     \
+    } while (0)
+    if (dtype == IRGAN_F32) {
+        if (dz_dtype == IRGAN_BF16) TAP_LAUNCH(float, bf16_t);
+        else TAP_LAUNCH(float, float);
+    } else {
+        if (dz_dtype == IRGAN_BF16) TAP_LAUNCH(bf16_t, bf16_t);
+        else TAP_LAUNCH(bf16_t, float);
+    }
+#undef TAP_LAUNCH
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

@@ -1426,6 +1426,39 @@ class DiscriminatorEngine:
 # ----------------------------------------------------------------------------
 
 NO_POOL_FUSION = bool(os.environ.get("IRGAN_NO_POOL_FUSION"))   # A/B: separate conv and maxpool launches
+NO_TAP_FUSION = bool(os.environ.get("IRGAN_NO_TAP_FUSION"))     # A/B: maxpool_bwd, then the tap as its own launch
+
+# Config.perc_layers: torchvision's names of the ReLU maps of vgg16.features[:16]; the index is the
+# engine's conv number j (relu1_2 = 1 and relu2_2 = 3 feed the two MaxPool2d)
+PERC_LAYERS = ("relu1_1", "relu1_2", "relu2_1", "relu2_2", "relu3_1", "relu3_2", "relu3_3")
+DEFAULT_TAPS = (("relu3_3", 1.0),)   # the reference's perceptual term (ir:1667-1669)
+
+
+def perc_taps(layers, weights=None):
+    """The perceptual taps ((name, weight), ...) of ``layers`` / ``weights`` (None: every weight 1),
+    sorted by depth, zero-weight layers dropped.  ValueError for an unknown name, a duplicate, an
+    empty list, a weights length that differs from the layers', a weight that is not finite or
+    is negative, and all-zero weights."""
+    if isinstance(layers, str):
+        layers = (layers,)
+    layers = tuple(layers)
+    if not layers:
+        raise ValueError(f"perc_layers must name at least one of {PERC_LAYERS}, got an empty list")
+    for n in layers:
+        if n not in PERC_LAYERS:
+            raise ValueError(f"perc_layers: unknown layer {n!r}; the taps are {PERC_LAYERS}")
+    if len(set(layers)) != len(layers):
+        raise ValueError(f"perc_layers names a layer twice: {layers!r}")
+    weights = (1.0,) * len(layers) if weights is None else tuple(float(w) for w in weights)
+    if len(weights) != len(layers):
+        raise ValueError(f"perc_weights has {len(weights)} entries for {len(layers)} perc_layers")
+    for w in weights:
+        if not (math.isfinite(w) and w >= 0.0):
+            raise ValueError(f"perc_weights must be finite and >= 0, got {w!r}")
+    taps = tuple(sorted(((n, w) for n, w in zip(layers, weights) if w > 0.0), key=lambda t: PERC_LAYERS.index(t[0])))
+    if not taps:
+        raise ValueError("perc_weights are all zero: no perceptual term is left (set lambda_perc = 0 instead)")
+    return taps
 
 
 class VGGEngine:
@@ -1447,22 +1480,30 @@ class VGGEngine:
             self._pack_batch = ops.PackBatch(self.packs)
         self._pack_batch.run()
 
-    def forward(self, vin: Feat, bufs: Buffers = None, part=None, keep=True) -> Feat:
+    def forward(self, vin: Feat, bufs: Buffers = None, part=None, keep=True, taps=None) -> Feat:
         """relu3_3 features of vin.  part = (b0, nb): compute only images [b0, b0+nb)
         into the full-batch activation buffers (the step runs the real and the fake
         half on different streams).  keep=False: no backward will read these images'
         activations (the real half), so a conv followed by MaxPool2d may write the pooled
-        map alone (ops.conv_fwd_pool)."""
+        map alone (ops.conv_fwd_pool).
+
+        taps (perc_taps' pairs; None: the relu3_3 stack as it always ran): the stack stops at the
+        deepest tapped conv, whose map is returned (a pooled layer that ends the stack is not
+        pooled), and a tapped conv+pool layer writes its full-size map under keep=False too:
+        backward_taps reads it."""
         g, T = bufs or self.bufs, self.tdt
         x = vin
         acts = g.state["acts"] = [vin]
         sl = (lambda f: f) if part is None else (lambda f: f.batch(*part))  # noqa: E731
-        for j, pc in enumerate(self.packs):
+        tapped = () if taps is None else [PERC_LAYERS.index(n) for n, _ in taps]
+        last = max(tapped, default=len(self.packs) - 1)
+        for j, pc in enumerate(self.packs[:last + 1]):
             y = Feat(g.get(f"v{j}", (x.N, x.H, x.W, pc.spec.cout), T))
-            pooled = j in (1, 3)
+            pooled = j in (1, 3) and j < last
             if pooled:   # conv -> ReLU -> MaxPool2d(2) (ir:664), fused where a kernel takes the layer
                 p = Feat(g.get(f"p{j}", (x.N, x.H // 2, x.W // 2, pc.spec.cout), T))
-                if NO_POOL_FUSION or not ops.conv_fwd_pool(pc, sl(x), sl(y) if keep else None, sl(p)):
+                full = keep or j in tapped
+                if NO_POOL_FUSION or not ops.conv_fwd_pool(pc, sl(x), sl(y) if full else None, sl(p)):
                     ops.conv_fwd(pc, sl(x), sl(y), act=ACT_RELU)
                     ops.maxpool(sl(y), sl(p))
             else:
@@ -1503,6 +1544,56 @@ class VGGEngine:
             else:  # input is a ReLU output: fold relu' into the dgrad epilogue
                 dzn = Feat(g.get(f"dz{j - 1}", (nb, xin.H, xin.W, xin.C), T))
                 ops.conv_dgrad(pc, dz, dzn, mask=xin, mask_act=1)
+            dz = dzn
+        return None
+
+    def backward_taps(self, taps, nb: int, scale: float, loss: torch.Tensor, bufs: Buffers = None) -> Feat:
+        """The multi-layer perceptual term (Config.perc_layers) after forward(..., taps=taps) ran on
+        both halves of a 2*nb batch (fake images [0, nb), real images [nb, 2 nb)):
+        ``loss`` += scale * sum_l w_l * mean|phi_l(fake) - phi_l(real)|, and d(input) of that sum
+        for the fake images is returned.  backward_input's walk, begun at the deepest tap; each
+        shallower tap adds its gradient to the dz of its layer on the way down: a tapped pool input
+        inside the pool backward (ops.maxpool_bwd_tap; NO_TAP_FUSION or a refused shape: maxpool_bwd,
+        then l1_tap over the whole map), any other layer by l1_tap on what the dgrad epilogue wrote."""
+        g, T = bufs or self.bufs, self.tdt
+        fake = [a.batch(0, nb) for a in g.state["acts"]]
+        real = [a.batch(nb, nb) for a in g.state["acts"]]
+        out_of = {0: 1, 1: 2, 2: 4, 3: 5, 4: 7, 5: 8, 6: 9}     # conv j output index in acts
+        in_of = {0: 0, 1: 1, 2: 3, 3: 4, 4: 6, 5: 7, 6: 8}      # conv j input index in acts
+        wt = {PERC_LAYERS.index(n): scale * w for n, w in taps}
+
+        def tap(j, dz, accumulate):
+            ops.l1_tap(fake[out_of[j]].t, real[out_of[j]].t, wt[j], dz.t, loss, accumulate)
+
+        top = max(wt)
+        src = fake[out_of[top]]
+        dz = Feat(g.get(f"dz{top}", (nb, src.H, src.W, src.C), T))
+        tap(top, dz, False)
+        for j in range(top, -1, -1):
+            pc = self.packs[j]
+            xin = fake[in_of[j]]
+            if j == 0:
+                dvin = Feat(g.get("dvin", (nb, xin.H, xin.W, pc.spec.cin), torch.float32))
+                ops.conv_dgrad(pc, dz, dvin)
+                return dvin
+            prev = in_of[j]
+            if prev in (3, 6):  # input is a pool output: dgrad -> maxpool bwd (+relu') of the pool input
+                dp = Feat(g.get(f"dp{j}", (nb, xin.H, xin.W, xin.C), T))
+                ops.conv_dgrad(pc, dz, dp)
+                src = fake[prev - 1]
+                dzn = Feat(g.get(f"dz{j - 1}", (nb, src.H, src.W, src.C), T))
+                if j - 1 not in wt or NO_TAP_FUSION or \
+                        not ops.maxpool_bwd_tap(src, real[prev - 1], dp, dzn, wt[j - 1], loss):
+                    if src.H % 2 or src.W % 2:   # floor pooling: the last odd row / column gets no gradient
+                        dzn.t.zero_()
+                    ops.maxpool_bwd(src, dp, dzn, relu_mask=True)
+                    if j - 1 in wt:
+                        tap(j - 1, dzn, True)
+            else:  # input is a ReLU output: fold relu' into the dgrad epilogue
+                dzn = Feat(g.get(f"dz{j - 1}", (nb, xin.H, xin.W, xin.C), T))
+                ops.conv_dgrad(pc, dz, dzn, mask=xin, mask_act=1)
+                if j - 1 in wt:
+                    tap(j - 1, dzn, True)
             dz = dzn
         return None
 
@@ -1705,6 +1796,11 @@ class GANStep:
         self.gan_real_label = float(getattr(cfg, "gan_real_label", 1.0))
         if self.gan_mode not in ops.GAN_MODES:
             raise ValueError(f"gan_mode must be one of {sorted(ops.GAN_MODES)}, got {self.gan_mode!r}")
+        # Config.perc_layers / perc_weights: the VGG maps of the perceptual term.  None is the
+        # reference's relu3_3 at weight 1, whose launches (ops.l1 into dfeat, backward_input) are
+        # untouched; any other setting goes through VGGEngine.backward_taps
+        taps = perc_taps(getattr(cfg, "perc_layers", ("relu3_3",)), getattr(cfg, "perc_weights", None))
+        self.perc_taps = None if taps == DEFAULT_TAPS else taps
         # the D step (D forward/backward on [real; fake] and its all-reduce) runs on a
         # side stream, concurrently with the G-step terms that do not read D (L1,
         # VGG, TV, SSIM); IRGAN_NO_D_OVERLAP=1 keeps everything on one stream
@@ -1751,7 +1847,8 @@ class GANStep:
                     ops.nchw_to_nhwc(ir.contiguous(), Feat(din.t[h:h + B], 0, cin))
                 ops.axpby(Feat(rgb_h), 1.0, Feat(din.t[:B], cin, cout))
                 ops.affine(Feat(rgb_h), self.vgg.scale, self.vgg.shift, vin.batch(B, B))
-                self.vgg.forward(vin, part=(B, B), keep=False)   # no backward through the real half
+                # no backward through the real half
+                self.vgg.forward(vin, part=(B, B), keep=False, taps=self.perc_taps)
             if vgg_side:
                 _mark(ph, "vgg_real", self.side)
                 ev = torch.cuda.Event()
@@ -1780,12 +1877,15 @@ class GANStep:
             ops.l1(fake, rgb_h, cfg.lambda_L1, dfake, L[2:3], accumulate=True)
             # perceptual (ir:1667-1669): VGG on the fake half; the real half ran on the side stream
             ops.affine(Feat(fake), self.vgg.scale, self.vgg.shift, vin.batch(0, B))
-            feat = self.vgg.forward(vin, part=(0, B))
+            feat = self.vgg.forward(vin, part=(0, B), taps=self.perc_taps)
             if ev_vgg is not None:
                 main.wait_event(ev_vgg)
-            dfeat = b.get("dfeat", (B, feat.H, feat.W, feat.C), T)
-            ops.l1(feat.t[:B], feat.t[B:], cfg.lambda_perc, dfeat, L[3:4])
-            dv = self.vgg.backward_input(Feat(dfeat), B)
+            if self.perc_taps is None:
+                dfeat = b.get("dfeat", (B, feat.H, feat.W, feat.C), T)
+                ops.l1(feat.t[:B], feat.t[B:], cfg.lambda_perc, dfeat, L[3:4])
+                dv = self.vgg.backward_input(Feat(dfeat), B)
+            else:   # Config.perc_layers: every tap's term lands in slot 3, times lambda_perc * w_l
+                dv = self.vgg.backward_taps(self.perc_taps, B, cfg.lambda_perc, L[3:4])
             ops.affine(dv, self.vgg.scale, None, Feat(dfake), accumulate=True)
             ops.tv(Feat(fake), cfg.lambda_tv, dfake, L[4:5])
             ssim_work = b.flat("ssim_work", 10 * fake.numel())

@@ -8,7 +8,7 @@ path and the pieces a train/test driver touches:
     ResnetUNetGenerator (ir:425), NLayerDiscriminator (ir:576),
     VGGPerceptual (ir:642), tv_loss (ir:686), ssim_loss_torch (ir:714),
     gan_loss_D / gan_loss_G (the step's GAN objective, Config.gan_mode: ir:1647-1662 and
-    the LSGAN / BCE forms),
+    the LSGAN / BCE forms), perceptual_loss (the step's perceptual term, Config.perc_layers),
     IRColorizationModel (ir:757), validate_kaist (ir:1521), train_kaist (ir:1549),
     and the test-mode names re-exported from inference.py / evaluation.py:
     ir_to_tensor, tensor_to_rgb_image, compute_metrics, save_best_k_outputs,
@@ -36,12 +36,12 @@ import torch.nn as nn
 
 from . import ops
 from .engine import (Buffers, DiscriminatorEngine, GANStep, GeneratorEngine, ParamStore, VGGEngine, d_layers,
-                     d_param_shapes, g_param_shapes, res_conv_keys, vgg_param_shapes)
+                     d_param_shapes, g_param_shapes, perc_taps, res_conv_keys, vgg_param_shapes)
 from .ops import BF16, F32, Feat
 
 __all__ = ["Config", "Identity", "get_norm_layer", "init_weights", "init_net", "get_lr_lambda", "get_filter",
            "ResnetUNetGenerator", "NLayerDiscriminator", "VGGPerceptual", "tv_loss", "ssim_loss_torch",
-           "gan_loss_D", "gan_loss_G",
+           "gan_loss_D", "gan_loss_G", "perceptual_loss",
            "IRColorizationModel", "GANTrainer", "validate_kaist", "train_kaist", "SyntheticPairDataset",
            "g_param_shapes", "d_param_shapes", "vgg_param_shapes", "seeded_state", "dp_loaders", "val_shard",
            "compute_metrics", "save_best_k_outputs", "run_test", "make_comparison_collage", "save_comparison_image",
@@ -119,6 +119,9 @@ class Config:
                                          # 1662), "lsgan" (least squares) or "vanilla" (BCE with logits)
         self.gan_real_label = 1.0        # D's target for real patches, in (0, 1]: < 1 is one-sided label
                                          # smoothing (lsgan / vanilla only; G's target stays 1)
+        self.perc_layers = ("relu3_3",)  # the VGG maps of the perceptual term (engine.PERC_LAYERS: relu1_1 ..
+                                         # relu3_3); loss_G_perc = lambda_perc * sum_l w_l * mean|phi_l(fake) -
+        self.perc_weights = None         # phi_l(rgb)|, w_l = perc_weights (None: every layer at weight 1)
 
 
 # =============================================================================
@@ -677,6 +680,50 @@ def gan_loss_G(pred_fake, mode="hinge"):
     return _GANLossFn.apply(1, mode, 1.0, pred_fake)
 
 
+class _PercFn(torch.autograd.Function):
+    """VGGEngine.forward / backward_taps on its own Buffers: the forward gives the value and
+    d fake together, backward scales d fake by the upstream gradient.  The same kernels and taps
+    as the fused step's, so a hand-written loop gets its gradients."""
+
+    @staticmethod
+    def forward(ctx, fake, real, mod, taps):
+        eng, B = mod.engine, fake.shape[0]
+        bufs = Buffers(fake.device)
+        mod._maybe_repack()
+        both = torch.cat([fake.detach(), real.detach()]).float()
+        vin = _nhwc_input(both, eng.packs[0], eng.tdt, eng.scale, eng.shift)
+        eng.forward(vin, bufs=bufs, part=(B, B), keep=False, taps=taps)
+        eng.forward(vin, bufs=bufs, part=(0, B), taps=taps)
+        loss = torch.zeros(1, dtype=torch.float64, device=fake.device)
+        dv = eng.backward_taps(taps, B, 1.0, loss, bufs=bufs)
+        dimg = torch.zeros(dv.N, dv.H, dv.W, dv.C, device=fake.device)
+        ops.affine(dv, eng.scale, None, Feat(dimg))
+        grad = torch.empty(dv.N, dv.C, dv.H, dv.W, device=fake.device)
+        ops.nhwc_to_nchw(Feat(dimg), grad)
+        ctx.save_for_backward(grad)
+        return loss.float()[0]
+
+    @staticmethod
+    def backward(ctx, gl):
+        (grad,) = ctx.saved_tensors
+        return grad * gl, None, None, None
+
+
+def perceptual_loss(vgg, fake, real, layers=("relu3_3",), weights=None):
+    """The fused step's perceptual term before lambda_perc (Config.perc_layers / perc_weights):
+    sum_l w_l * mean|phi_l(fake) - phi_l(real)| over the ReLU maps ``layers`` of ``vgg`` (a
+    VGGPerceptual; names: engine.PERC_LAYERS, weights None: all 1), each mean over that layer's
+    own B*C*H*W.  ``fake`` and ``real`` are NCHW images in [-1, 1] of one shape.  A scalar with
+    autograd to ``fake``; ``real`` gets no gradient."""
+    taps = perc_taps(layers, weights)
+    _require_cuda(fake, "perceptual_loss")
+    _require_cuda(real, "perceptual_loss")
+    if fake.shape != real.shape or fake.dim() != 4:
+        raise ValueError(f"perceptual_loss: fake and real are NCHW images of one shape, got "
+                         f"{tuple(fake.shape)} and {tuple(real.shape)}")
+    return _PercFn.apply(fake, real, vgg, taps)
+
+
 # =============================================================================
 # 7) Model wrapper (ir:757-796)
 # =============================================================================
@@ -774,6 +821,14 @@ def _check_gan(cfg):
     return mode, t
 
 
+def _check_perc(cfg):
+    """The perceptual taps ((layer, weight), ...) of Config.perc_layers / perc_weights, sorted by
+    depth, zero-weight layers dropped (engine.perc_taps).  ValueError for an unknown name, a
+    duplicate, an empty list, a weights length that differs from the layers', a weight that is
+    not finite or is negative, and all-zero weights."""
+    return perc_taps(getattr(cfg, "perc_layers", ("relu3_3",)), getattr(cfg, "perc_weights", None))
+
+
 class GANTrainer:
     """Owns G (through the model), D, VGG and both Adams; ``step(ir, rgb)`` runs
     the fused HIP train step and returns the device loss vector (no host sync)."""
@@ -787,6 +842,7 @@ class GANTrainer:
         self.ema_decay = _check_ema_decay(cfg)              # likewise
         self.clip_grad_G, self.clip_grad_D = _check_clip_grad(cfg)
         self.gan_mode, self.gan_real_label = _check_gan(cfg)
+        self.perc_taps = _check_perc(cfg)
         dev = torch.device(cfg.device)
         dt = getattr(cfg, "compute_dtype", "bf16")
         if getattr(cfg, "deterministic", False):
@@ -1053,6 +1109,7 @@ def train_kaist(cfg: Config, dataset=None, log=print, trainer_hook=None):
         model.load_weights(cfg.init_G_weights, log=log)
     trainer = GANTrainer(cfg, model=model)
     log(f"GAN objective: {trainer.gan_mode} (real label {trainer.gan_real_label:g})")
+    log("Perceptual layers: " + ", ".join(f"{n} x {w:g}" for n, w in trainer.perc_taps))
     if trainer_hook is not None:
         trainer_hook(trainer)
     if rank == 0:

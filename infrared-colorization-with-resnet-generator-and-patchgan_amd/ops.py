@@ -1138,6 +1138,19 @@ def maxpool_bwd(x: Feat, dy: Feat, dx: Feat, relu_mask=True):
     _lib.call("irgan_maxpool_bwd", x.ptr, dy.ptr, x.dt, x.N, x.H, x.W, x.C, dx.ptr, int(relu_mask), stream())
 
 
+def maxpool_bwd_tap(x: Feat, xr: Feat, dy: Feat, dx: Feat, w: float, loss: torch.Tensor) -> bool:
+    """maxpool_bwd(relu_mask=True) of a pool input that is a perceptual tap: dx also receives the
+    tap's gradient (x > 0 ? sgn(x - xr) * w / count : 0) and ``loss`` += w * mean|x - xr|, in the
+    one launch (irgan_maxpool_bwd_tap).  False when the library refuses the shape (an odd side)
+    -- then NOTHING ran and the caller does maxpool_bwd + l1_tap(accumulate=True)."""
+    for f in (x, xr, dy, dx):
+        assert f.off == 0 and f.C == f.ld and f.dt == x.dt
+    assert (xr.N, xr.H, xr.W, xr.C) == (x.N, x.H, x.W, x.C) == (dx.N, dx.H, dx.W, dx.C)
+    assert (dy.N, dy.H, dy.W, dy.C) == (x.N, x.H // 2, x.W // 2, x.C)
+    return _try("irgan_maxpool_bwd_tap", x.ptr, xr.ptr, dy.ptr, x.dt, x.N, x.H, x.W, x.C, dx.ptr,
+                ctypes.c_float(w), P(loss), stream())
+
+
 def nchw_to_nhwc(x: torch.Tensor, y: Feat, scale=None, shift=None):
     N, C, H, W = x.shape
     _lib.call("irgan_nchw_to_nhwc", P(x), N, C, H, W, y.ptr, y.dt, y.ld, y.off, P(scale), P(shift), stream())
@@ -1188,6 +1201,15 @@ def gan_loss(pred: torch.Tensor, n_half: int, side: int, mode: str, real_label: 
 def l1(a: torch.Tensor, b: torch.Tensor, w: float, ga: torch.Tensor, loss: torch.Tensor, accumulate=False):
     _lib.call("irgan_l1", P(a), P(b), dt_code(a), a.numel(), ctypes.c_float(w), P(ga),
               dt_code(ga) if ga is not None else 0, int(accumulate), P(loss), stream())
+
+
+def l1_tap(a: torch.Tensor, b: torch.Tensor, w: float, dz: torch.Tensor, loss: torch.Tensor, accumulate=False):
+    """One perceptual tap (irgan_l1_tap): a / b the fake / real post-ReLU features, dz the gradient
+    w.r.t. the layer's pre-activation.  ``loss`` += w * mean|a - b|;
+    dz = (accumulate ? dz : 0) + (a > 0 ? sgn(a - b) * w / count : 0)."""
+    assert a.numel() == b.numel() == dz.numel() and a.dtype == b.dtype
+    _lib.call("irgan_l1_tap", P(a), P(b), dt_code(a), a.numel(), ctypes.c_float(w), P(dz), dt_code(dz),
+              int(accumulate), P(loss), stream())
 
 
 def _whole(x: Feat, what: str):
