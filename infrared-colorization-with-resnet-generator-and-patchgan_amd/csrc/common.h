@@ -37,6 +37,12 @@ template <typename T> IRGAN_HD T from_f(float v);
 template <> IRGAN_HD float from_f<float>(float v) { return v; }
 template <> IRGAN_HD bf16_t from_f<bf16_t>(float v) { return f2bf(v); }
 
+IRGAN_HD float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+// One perceptual tap (Config.perc_layers) per element: a = relu(z) of the fake images, b the real
+// images' map, inv = weight / count; d(inv * |a - b|) / dz.  The one definition: the tap fused into
+// the pool backward (resample.hip) and the tap on its own (loss.hip) agree bit for bit.
+IRGAN_HD float tap_grad(float a, float b, float inv) { return a > 0.f ? sgn(a - b) * inv : 0.f; }
+
 IRGAN_HD int reflect_idx(int q, int n) {  // nn.ReflectionPad2d index map (|pad| < n)
     q = q < 0 ? -q : q;
     return q >= n ? 2 * n - 2 - q : q;

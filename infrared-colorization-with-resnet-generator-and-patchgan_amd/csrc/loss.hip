@@ -10,8 +10,6 @@ constexpr int TPB = 256;
 
 IRGAN_HD void block_add(double* dst, float v) { block_sum_add<TPB>(dst, v); }
 
-IRGAN_HD float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
-
 int nblocks(long total) { return (int)std::max<long>(1, std::min<long>((total + TPB - 1) / TPB, 8192)); }
 // kernels that finish with block_add: every block adds into the SAME fp64 word,
 // and same-address atomics serialise at the memory side (~10 ns each), so keep
@@ -113,31 +111,39 @@ IRGAN_HD void st8t(T* p, long i, const float* v) {
     }
 }
 
+// loss += w * mean|a - b|, and the term's gradient written or added (accumulate) to ga, summed in
+// fp32 and rounded once to ga's type.  Plain: d/da = sgn(a-b) * w/count, ga may be null (value
+// only).  TAP, one perceptual tap (Config.perc_layers): a = relu(z) of the fake images, b the real
+// images' map, and the gradient w.r.t. the PRE-activation z lands in ga (required):
+//   dz = (accumulate ? dz : 0) + (a > 0 ? sgn(a-b) * w/count : 0)
 // VEC: 8 elements per thread-iteration (16/32-byte accesses; count % 8 == 0)
-template <typename T, typename G, bool VEC>
+template <typename T, typename G, bool VEC, bool TAP>
 __global__ __launch_bounds__(TPB) void l1_kernel(const T* __restrict__ a, const T* __restrict__ b, long count, float w,
                                                  G* __restrict__ ga, int accumulate, double* __restrict__ loss) {
     float acc = 0.f;
     const float inv = w / (float)count;
+    const bool wr = TAP || ga, rd = wr && accumulate;
     if constexpr (VEC) {
         for (long i = (blockIdx.x * (long)TPB + threadIdx.x) * 8; i < count; i += (long)gridDim.x * TPB * 8) {
             float av[8], bv[8], gv[8];
             ld8t<T>(a, i, av);
             ld8t<T>(b, i, bv);
-            if (ga && accumulate) ld8t<G>(ga, i, gv);
+            if (rd) ld8t<G>(ga, i, gv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float d = av[k] - bv[k];
                 acc += fabsf(d);
-                gv[k] = (ga && accumulate ? gv[k] : 0.f) + sgn(d) * inv;
+                gv[k] = (rd ? gv[k] : 0.f) + (TAP ? tap_grad(av[k], bv[k], inv) : sgn(d) * inv);
             }
-            if (ga) st8t<G>(ga, i, gv);
+            if (wr) st8t<G>(ga, i, gv);
         }
     } else {
         for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < count; i += (long)gridDim.x * TPB) {
-            const float d = to_f<T>(a[i]) - to_f<T>(b[i]);
+            const float av = to_f<T>(a[i]), bv = to_f<T>(b[i]), d = av - bv;
             acc += fabsf(d);
-            if (ga) {
+            if constexpr (TAP) {
+                ga[i] = from_f<G>((accumulate ? to_f<G>(ga[i]) : 0.f) + tap_grad(av, bv, inv));
+            } else if (ga) {
                 float gv = sgn(d) * inv;
                 if (accumulate) gv += to_f<G>(ga[i]);
                 ga[i] = from_f<G>(gv);
@@ -147,40 +153,6 @@ __global__ __launch_bounds__(TPB) void l1_kernel(const T* __restrict__ a, const 
     block_add(loss, acc * inv);
 }
 
-// One perceptual tap (Config.perc_layers): a = relu(z) of the fake images, b the real images'
-// map; loss += w*mean|a-b| and the term's gradient w.r.t. the PRE-activation z lands in dz:
-//   dz = (accumulate ? dz : 0) + (a > 0 ? sgn(a-b) * w/count : 0)
-// summed in fp32 and rounded once to dz's type.  l1_kernel's two forms.
-IRGAN_HD float tap_grad(float a, float b, float inv) { return a > 0.f ? sgn(a - b) * inv : 0.f; }
-
-template <typename T, typename G, bool VEC>
-__global__ __launch_bounds__(TPB) void l1_tap_kernel(const T* __restrict__ a, const T* __restrict__ b, long count,
-                                                     float w, G* __restrict__ dz, int accumulate,
-                                                     double* __restrict__ loss) {
-    float acc = 0.f;
-    const float inv = w / (float)count;
-    if constexpr (VEC) {
-        for (long i = (blockIdx.x * (long)TPB + threadIdx.x) * 8; i < count; i += (long)gridDim.x * TPB * 8) {
-            float av[8], bv[8], gv[8];
-            ld8t<T>(a, i, av);
-            ld8t<T>(b, i, bv);
-            if (accumulate) ld8t<G>(dz, i, gv);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                acc += fabsf(av[k] - bv[k]);
-                gv[k] = (accumulate ? gv[k] : 0.f) + tap_grad(av[k], bv[k], inv);
-            }
-            st8t<G>(dz, i, gv);
-        }
-    } else {
-        for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < count; i += (long)gridDim.x * TPB) {
-            const float av = to_f<T>(a[i]), bv = to_f<T>(b[i]);
-            acc += fabsf(av - bv);
-            dz[i] = from_f<G>((accumulate ? to_f<G>(dz[i]) : 0.f) + tap_grad(av, bv, inv));
-        }
-    }
-    block_add(loss, acc * inv);
-}
 
 // TV (ir:686-694): mean|x[h+1]-x[h]| + mean|x[w+1]-x[w]| over N*C*(H-1)*W and N*C*H*(W-1).
 // Grid-stride over image rows (n*H + y), threads over pixels x, channel loop.
@@ -676,63 +648,44 @@ extern "C" int irgan_gan_loss(const float* pred, int32_t n_half, int32_t side, i
     return 0;
 }
 
-extern "C" int irgan_l1(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* ga,
-                        int32_t ga_dtype, int32_t accumulate, double* loss, irgan_stream_t s) {
-    hipStream_t st = (hipStream_t)s;
+// l1_kernel<.., TAP> for the dtypes of a / b and of ga: the 8-wide form where count and every
+// pointer allow 16-byte accesses
+template <bool TAP>
+static int l1_launch(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* ga, int32_t ga_dtype,
+                     int32_t accumulate, double* loss, irgan_stream_t s) {
     if (count <= 0) return 0;
     const bool vec = count % 8 == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) &&
                      (!ga || (uintptr_t)ga % 16 == 0);
     const int nb = nblocks_red(vec ? count / 8 : count);
-#define L1_LAUNCH(T, G)                                                                                       \
-    do {                                                                                                      \
-        if (vec)                                                                                              \
-            l1_kernel<T, G, true><<<nb, TPB, 0, st>>>((const T*)a, (const T*)b, count, w, (G*)ga, accumulate, \
-                                                      loss);                                                  \
-        else                                                                                                  \
-            l1_kernel<T, G, false><<<nb, TPB, 0, st>>>((const T*)a, (const T*)b, count, w, (G*)ga, accumulate, \
-                                                       loss);                                                 \
-    } while (0)
+    auto go = [&](auto t, auto g) {
+        using T = decltype(t);
+        using G = decltype(g);
+        auto k = vec ? l1_kernel<T, G, true, TAP> : l1_kernel<T, G, false, TAP>;
+        k<<<nb, TPB, 0, (hipStream_t)s>>>((const T*)a, (const T*)b, count, w, (G*)ga, accumulate, loss);
+    };
     if (dtype == IRGAN_F32) {
-        if (ga_dtype == IRGAN_BF16) L1_LAUNCH(float, bf16_t);
-        else L1_LAUNCH(float, float);
+        if (ga_dtype == IRGAN_BF16) go(float(), bf16_t());
+        else go(float(), float());
     } else {
-        if (ga_dtype == IRGAN_BF16) L1_LAUNCH(bf16_t, bf16_t);
-        else L1_LAUNCH(bf16_t, float);
+        if (ga_dtype == IRGAN_BF16) go(bf16_t(), bf16_t());
+        else go(bf16_t(), float());
     }
-#undef L1_LAUNCH
     IRGAN_LAUNCH_CHECK();
     return 0;
 }
 
+extern "C" int irgan_l1(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* ga,
+                        int32_t ga_dtype, int32_t accumulate, double* loss, irgan_stream_t s) {
+    return l1_launch<false>(a, b, dtype, count, w, ga, ga_dtype, accumulate, loss, s);
+}
+
 extern "C" int irgan_l1_tap(const void* a, const void* b, int32_t dtype, int64_t count, float w, void* dz,
                             int32_t dz_dtype, int32_t accumulate, double* loss, irgan_stream_t s) {
-    hipStream_t st = (hipStream_t)s;
     if ((dtype != IRGAN_F32 && dtype != IRGAN_BF16) || (dz_dtype != IRGAN_F32 && dz_dtype != IRGAN_BF16) || !dz)
         return IRGAN_EINVAL;
-    if (count <= 0) return 0;
-    const bool vec = count % 8 == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) &&
-                     ((uintptr_t)dz % 16 == 0);
-    const int nb = nblocks_red(vec ? count / 8 : count);
-#define TAP_LAUNCH(T, G)                                                                                          \
-    do {                                                                                                          \
-        if (vec)                                                                                                  \
-            l1_tap_kernel<T, G, true><<<nb, TPB, 0, st>>>((const T*)a, (const T*)b, count, w, (G*)dz, accumulate, \
-                                                          loss);                                                  \
-        else                                                                                                      \
-            l1_tap_kernel<T, G, false><<<nb, TPB, 0, st>>>((const T*)a, (const T*)b, count, w, (G*)dz,            \
-                                                           accumulate, loss);                                     \
-    } while (0)
-    if (dtype == IRGAN_F32) {
-        if (dz_dtype == IRGAN_BF16) TAP_LAUNCH(float, bf16_t);
-        else TAP_LAUNCH(float, float);
-    } else {
-        if (dz_dtype == IRGAN_BF16) TAP_LAUNCH(bf16_t, bf16_t);
-        else TAP_LAUNCH(bf16_t, float);
-    }
-#undef TAP_LAUNCH
-    IRGAN_LAUNCH_CHECK();
-    return 0;
+    return l1_launch<true>(a, b, dtype, count, w, dz, dz_dtype, accumulate, loss, s);
 }
+
 
 extern "C" int irgan_tv(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, float w, float* g, double* loss,
                         irgan_stream_t s) {

@@ -699,39 +699,71 @@ __global__ __launch_bounds__(TPB) void maxpool_fwd_kernel(const void* __restrict
     stvec<VW>(y, dt, (((long)n * Ho + i) * Wo + j) * C + c, m);
 }
 
-// gradient routed to the (first) argmax; relu_mask folds the ReLU' of the pool input
-template <int VW>
-__global__ __launch_bounds__(TPB) void maxpool_bwd_kernel(const void* __restrict__ x, const void* __restrict__ dy,
-                                                          int dt, int H, int W, int C, void* __restrict__ dx,
-                                                          int relu_mask) {
+// The pool backward: the gradient routed to the (first) argmax; relu_mask folds the ReLU' of the
+// pool input.  Plain (TAP = false): one block row per pooled row (gridDim.y = N * (H/2)), odd H / W
+// floor-pooled, and xr, w, count, NR, loss unused.
+//
+// TAP, the pool backward of a TAPPED pool input (Config.perc_layers: relu1_2 / relu2_2): relu_mask
+// taken as 1, and the layer's perceptual term against the real images' map xr applied at all four
+// window positions:
+//   dx[q] = (argmax == q && max > 0 ? dy : 0) + (x[q] > 0 ? sgn(x[q] - xr[q]) * w/count : 0)
+//   loss += w/count * sum |x - xr|
+// i.e. the plain arm followed by loss.hip's l1_kernel<.., TAP> (accumulate) without re-reading and
+// re-writing dx: both round the same fp32 sum once, so dx is bit-identical to that pair.  Even H
+// and W only (the launcher checks): the window loop then visits every element of the map.
+// Blocks stride over the NR pooled rows (blockIdx.y, += gridDim.y <= NR; the launcher caps the grid
+// near 2048 blocks): every block ends in ONE fp64 atomic on the loss word, and a block per pooled
+// row (16384 blocks for relu1_2 at 256 x 256, B = 16) would queue that many on one address.
+template <int VW, bool TAP>
+__global__ __launch_bounds__(TPB) void maxpool_bwd_kernel(const void* __restrict__ x, const void* __restrict__ xr,
+                                                          const void* __restrict__ dy, int dt, int H, int W, int C,
+                                                          void* __restrict__ dx, int relu_mask, float w, long count,
+                                                          int NR, double* __restrict__ loss) {
     const int Ho = H / 2, Wo = W / 2, CV = C / VW;
     const int e = blockIdx.x * TPB + threadIdx.x;
-    if (e >= Wo * CV) return;
+    const bool on = e < Wo * CV;
+    if (!TAP && !on) return;   // TAP: no early return, block_sum_add is a block-wide reduction
     const int j = e / CV, c = (e - j * CV) * VW;
-    const int n = blockIdx.y / Ho, i = blockIdx.y - n * Ho;
-    float xv[4][VW], m[VW];
-    int am[VW];
+    const float inv = w / (float)count;
+    float acc = 0.f;
+    int row = blockIdx.y;
+    do {
+        if (on) {
+            const int n = row / Ho, i = row - n * Ho;
+            float xv[4][VW], m[VW];
+            int am[VW];
 #pragma unroll
-    for (int k = 0; k < VW; ++k) { m[k] = -INFINITY; am[k] = 0; }
+            for (int k = 0; k < VW; ++k) { m[k] = -INFINITY; am[k] = 0; }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        ldvec<VW>(x, dt, (((long)n * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C + c, xv[q]);
+            for (int q = 0; q < 4; ++q) {
+                ldvec<VW>(x, dt, (((long)n * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C + c, xv[q]);
 #pragma unroll
-        for (int k = 0; k < VW; ++k)
-            if (xv[q][k] > m[k] || isnan(xv[q][k])) { m[k] = xv[q][k]; am[k] = q; }
-    }
-    float g[VW];
-    ldvec<VW>(dy, dt, (((long)n * Ho + i) * Wo + j) * C + c, g);
+                for (int k = 0; k < VW; ++k)
+                    if (xv[q][k] > m[k] || isnan(xv[q][k])) { m[k] = xv[q][k]; am[k] = q; }
+            }
+            float g[VW];
+            ldvec<VW>(dy, dt, (((long)n * Ho + i) * Wo + j) * C + c, g);
 #pragma unroll
-    for (int k = 0; k < VW; ++k)
-        if (relu_mask && !(m[k] > 0.f)) g[k] = 0.f;
+            for (int k = 0; k < VW; ++k)
+                if ((TAP || relu_mask) && !(m[k] > 0.f)) g[k] = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float o[VW];
+            for (int q = 0; q < 4; ++q) {
+                const long at = (((long)n * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C + c;
+                float r[VW], o[VW];
+                if constexpr (TAP) ldvec<VW>(xr, dt, at, r);
 #pragma unroll
-        for (int k = 0; k < VW; ++k) o[k] = am[k] == q ? g[k] : 0.f;
-        stvec<VW>(dx, dt, (((long)n * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C + c, o);
-    }
+                for (int k = 0; k < VW; ++k) {
+                    o[k] = am[k] == q ? g[k] : 0.f;
+                    if constexpr (TAP) {
+                        acc += fabsf(xv[q][k] - r[k]);
+                        o[k] += tap_grad(xv[q][k], r[k], inv);
+                    }
+                }
+                stvec<VW>(dx, dt, at, o);
+            }
+        }
+    } while (TAP && (row += gridDim.y) < NR);
+    if constexpr (TAP) block_sum_add<TPB>(loss, acc * inv);
 }
 
 // The bf16 form for C = 8 CL channels (CL = 8, 16, 32: the VGG pools, C = 64 / 128 / 256), laid
@@ -746,129 +778,14 @@ IRGAN_HD uint32_t xchg(uint32_t v) {   // value of lane ^ CL
     if constexpr (CL < 16) return (uint32_t)__float_as_int(dpp_xor16<CL>(__int_as_float((int)v)));
     else return (uint32_t)__shfl_xor((int)v, CL, 64);
 }
-template <int CL>
-__global__ __launch_bounds__(TPB) void maxpool_bwd_rows_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
-                                                               int H, int W, bf16_t* __restrict__ dx, int relu_mask) {
-    constexpr int C = CL * 8, PPW = 64 / (2 * CL);  // pooled pixels per wave
-    const int Ho = H / 2, Wo = W / 2;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int n = blockIdx.y / Ho, i = blockIdx.y - n * Ho;
-    const int b = (lane / CL) & 1, ch = lane % CL;
-    const int j = (blockIdx.x * (TPB / 64) + wv) * PPW + lane / (2 * CL);
-    const bool on = j < Wo;   // whole pixel groups: the partner lane has the same j
-    const long r0 = ((long)n * H + 2 * i) * W + 2 * j + b, r1 = r0 + W;
-    uint4 x0 = make_uint4(0u, 0u, 0u, 0u), x1 = x0, g4 = x0;
-    if (on) {
-        x0 = *(const uint4*)(x + r0 * C + ch * 8);
-        x1 = *(const uint4*)(x + r1 * C + ch * 8);
-        g4 = *(const uint4*)(dy + (((long)n * Ho + i) * Wo + j) * C + ch * 8);
-    }
-    const uint32_t own0[4] = {x0.x, x0.y, x0.z, x0.w}, own1[4] = {x1.x, x1.y, x1.z, x1.w};
-    uint32_t oth0[4], oth1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        oth0[k] = xchg<CL>(own0[k]);
-        oth1[k] = xchg<CL>(own1[k]);
-    }
-    if (!on) return;
-    const uint32_t gw[4] = {g4.x, g4.y, g4.z, g4.w};
-    uint32_t o0[4], o1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        // window order q = 2a + b': (0,0), (0,1), (1,0), (1,1)
-        const uint32_t q[4] = {b ? oth0[k] : own0[k], b ? own0[k] : oth0[k], b ? oth1[k] : own1[k],
-                               b ? own1[k] : oth1[k]};
-        float r[2][2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            float m = -INFINITY;
-            int am = 0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float v = __uint_as_float(h ? q[t] & 0xffff0000u : q[t] << 16);
-                if (v > m || isnan(v)) { m = v; am = t; }
-            }
-            float gv = __uint_as_float(h ? gw[k] & 0xffff0000u : gw[k] << 16);
-            if (relu_mask && !(m > 0.f)) gv = 0.f;
-            r[0][h] = am == b ? gv : 0.f;        // row 2i, this lane's column
-            r[1][h] = am == 2 + b ? gv : 0.f;    // row 2i + 1
-        }
-        o0[k] = pk_bf16(r[0][0], r[0][1]);
-        o1[k] = pk_bf16(r[1][0], r[1][1]);
-    }
-    *(uint4*)(dx + r0 * C + ch * 8) = make_uint4(o0[0], o0[1], o0[2], o0[3]);
-    *(uint4*)(dx + r1 * C + ch * 8) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
-}
-
-// The pool backward of a TAPPED pool input (Config.perc_layers: relu1_2 / relu2_2): the two kernels
-// above with relu_mask = 1 that also apply the layer's perceptual term against the real images'
-// map xr, at all four window positions:
-//   dx[q] = (argmax == q && max > 0 ? dy : 0) + (x[q] > 0 ? sgn(x[q] - xr[q]) * w/count : 0)
-//   loss += w/count * sum |x - xr|
-// i.e. maxpool_bwd followed by loss.hip's l1_tap_kernel (accumulate) without re-reading and
-// re-writing dx: both round the same fp32 sum once, so dx is bit-identical to that pair.  Even H
-// and W only (the launcher checks): the window loop then visits every element of the map.
-// Blocks stride over the pooled rows (blockIdx.y, += gridDim.y; the launcher caps the grid near
-// 2048 blocks): every block ends in ONE fp64 atomic on the loss word, and a block per pooled row
-// (16384 blocks for relu1_2 at 256 x 256, B = 16) would queue that many on one address.
-IRGAN_HD float tap_grad(float a, float b, float inv) {
-    const float d = a - b;
-    return a > 0.f ? (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * inv : 0.f;
-}
-
-template <int VW>
-__global__ __launch_bounds__(TPB) void maxpool_bwd_tap_kernel(const void* __restrict__ x, const void* __restrict__ xr,
-                                                              const void* __restrict__ dy, int dt, int H, int W, int C,
-                                                              void* __restrict__ dx, float w, long count,
-                                                              int NR, double* __restrict__ loss) {
-    const int Ho = H / 2, Wo = W / 2, CV = C / VW;
-    const int e = blockIdx.x * TPB + threadIdx.x;
-    const float inv = w / (float)count;
-    float acc = 0.f;
-    const int j = e / CV, c = (e - j * CV) * VW;
-    // no early return: block_sum_add is a block-wide reduction
-    for (int row = blockIdx.y; row < NR && e < Wo * CV; row += gridDim.y) {
-        const int n = row / Ho, i = row - n * Ho;
-        float xv[4][VW], m[VW];
-        int am[VW];
-#pragma unroll
-        for (int k = 0; k < VW; ++k) { m[k] = -INFINITY; am[k] = 0; }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            ldvec<VW>(x, dt, (((long)n * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C + c, xv[q]);
-#pragma unroll
-            for (int k = 0; k < VW; ++k)
-                if (xv[q][k] > m[k] || isnan(xv[q][k])) { m[k] = xv[q][k]; am[k] = q; }
-        }
-        float g[VW];
-        ldvec<VW>(dy, dt, (((long)n * Ho + i) * Wo + j) * C + c, g);
-#pragma unroll
-        for (int k = 0; k < VW; ++k)
-            if (!(m[k] > 0.f)) g[k] = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const long at = (((long)n * H + 2 * i + (q >> 1)) * W + 2 * j + (q & 1)) * C + c;
-            float r[VW], o[VW];
-            ldvec<VW>(xr, dt, at, r);
-#pragma unroll
-            for (int k = 0; k < VW; ++k) {
-                acc += fabsf(xv[q][k] - r[k]);
-                o[k] = (am[k] == q ? g[k] : 0.f) + tap_grad(xv[q][k], r[k], inv);
-            }
-            stvec<VW>(dx, dt, at, o);
-        }
-    }
-    block_sum_add<TPB>(loss, acc * inv);
-}
-
-// maxpool_bwd_rows_kernel's layout and lane exchange; each lane also loads its own two 16-byte
-// pieces of xr (its column of rows 2i and 2i + 1: the tap needs no partner values)
-template <int CL>
-__global__ __launch_bounds__(TPB) void maxpool_bwd_tap_rows_kernel(const bf16_t* __restrict__ x,
-                                                                   const bf16_t* __restrict__ xr,
-                                                                   const bf16_t* __restrict__ dy, int H, int W,
-                                                                   bf16_t* __restrict__ dx, float w, long count,
-                                                                   int NR, double* __restrict__ loss) {
+// TAP: each lane also loads its own two 16-byte pieces of xr (its column of rows 2i and 2i + 1: the
+// tap needs no partner values)
+template <int CL, bool TAP>
+__global__ __launch_bounds__(TPB) void maxpool_bwd_rows_kernel(const bf16_t* __restrict__ x,
+                                                               const bf16_t* __restrict__ xr,
+                                                               const bf16_t* __restrict__ dy, int H, int W,
+                                                               bf16_t* __restrict__ dx, int relu_mask, float w,
+                                                               long count, int NR, double* __restrict__ loss) {
     constexpr int C = CL * 8, PPW = 64 / (2 * CL);  // pooled pixels per wave
     const int Ho = H / 2, Wo = W / 2;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -877,7 +794,8 @@ __global__ __launch_bounds__(TPB) void maxpool_bwd_tap_rows_kernel(const bf16_t*
     const bool on = j < Wo;   // whole pixel groups: the partner lane has the same j
     const float inv = w / (float)count;
     float acc = 0.f;
-    for (int row = blockIdx.y; row < NR; row += gridDim.y) {   // block-uniform: every lane exchanges
+    int row = blockIdx.y;
+    do {   // block-uniform: every lane exchanges
         const int n = row / Ho, i = row - n * Ho;
         const long r0 = ((long)n * H + 2 * i) * W + 2 * j + b, r1 = r0 + W;
         uint4 x0 = make_uint4(0u, 0u, 0u, 0u), x1 = x0, g4 = x0, y0 = x0, y1 = x0;
@@ -885,8 +803,10 @@ __global__ __launch_bounds__(TPB) void maxpool_bwd_tap_rows_kernel(const bf16_t*
             x0 = *(const uint4*)(x + r0 * C + ch * 8);
             x1 = *(const uint4*)(x + r1 * C + ch * 8);
             g4 = *(const uint4*)(dy + (((long)n * Ho + i) * Wo + j) * C + ch * 8);
-            y0 = *(const uint4*)(xr + r0 * C + ch * 8);
-            y1 = *(const uint4*)(xr + r1 * C + ch * 8);
+            if constexpr (TAP) {
+                y0 = *(const uint4*)(xr + r0 * C + ch * 8);
+                y1 = *(const uint4*)(xr + r1 * C + ch * 8);
+            }
         }
         const uint32_t own0[4] = {x0.x, x0.y, x0.z, x0.w}, own1[4] = {x1.x, x1.y, x1.z, x1.w};
         uint32_t oth0[4], oth1[4];
@@ -895,7 +815,8 @@ __global__ __launch_bounds__(TPB) void maxpool_bwd_tap_rows_kernel(const bf16_t*
             oth0[k] = xchg<CL>(own0[k]);
             oth1[k] = xchg<CL>(own1[k]);
         }
-        if (on) {   // no early return: block_sum_add is a block-wide reduction
+        if (!TAP && !on) return;   // TAP: no early return, block_sum_add is a block-wide reduction
+        if (on) {
             const uint32_t gw[4] = {g4.x, g4.y, g4.z, g4.w};
             const uint32_t re0[4] = {y0.x, y0.y, y0.z, y0.w}, re1[4] = {y1.x, y1.y, y1.z, y1.w};
             uint32_t o0[4], o1[4];
@@ -915,14 +836,18 @@ __global__ __launch_bounds__(TPB) void maxpool_bwd_tap_rows_kernel(const bf16_t*
                         if (v > m || isnan(v)) { m = v; am = t; }
                     }
                     float gv = __uint_as_float(h ? gw[k] & 0xffff0000u : gw[k] << 16);
-                    if (!(m > 0.f)) gv = 0.f;
-                    const float a0 = __uint_as_float(h ? own0[k] & 0xffff0000u : own0[k] << 16);
-                    const float a1 = __uint_as_float(h ? own1[k] & 0xffff0000u : own1[k] << 16);
-                    const float b0 = __uint_as_float(h ? re0[k] & 0xffff0000u : re0[k] << 16);
-                    const float b1 = __uint_as_float(h ? re1[k] & 0xffff0000u : re1[k] << 16);
-                    acc += fabsf(a0 - b0) + fabsf(a1 - b1);
-                    r[0][h] = (am == b ? gv : 0.f) + tap_grad(a0, b0, inv);        // row 2i, this lane's column
-                    r[1][h] = (am == 2 + b ? gv : 0.f) + tap_grad(a1, b1, inv);    // row 2i + 1
+                    if ((TAP || relu_mask) && !(m > 0.f)) gv = 0.f;
+                    r[0][h] = am == b ? gv : 0.f;        // row 2i, this lane's column
+                    r[1][h] = am == 2 + b ? gv : 0.f;    // row 2i + 1
+                    if constexpr (TAP) {
+                        const float a0 = __uint_as_float(h ? own0[k] & 0xffff0000u : own0[k] << 16);
+                        const float a1 = __uint_as_float(h ? own1[k] & 0xffff0000u : own1[k] << 16);
+                        const float b0 = __uint_as_float(h ? re0[k] & 0xffff0000u : re0[k] << 16);
+                        const float b1 = __uint_as_float(h ? re1[k] & 0xffff0000u : re1[k] << 16);
+                        acc += fabsf(a0 - b0) + fabsf(a1 - b1);
+                        r[0][h] += tap_grad(a0, b0, inv);
+                        r[1][h] += tap_grad(a1, b1, inv);
+                    }
                 }
                 o0[k] = pk_bf16(r[0][0], r[0][1]);
                 o1[k] = pk_bf16(r[1][0], r[1][1]);
@@ -930,8 +855,8 @@ __global__ __launch_bounds__(TPB) void maxpool_bwd_tap_rows_kernel(const bf16_t*
             *(uint4*)(dx + r0 * C + ch * 8) = make_uint4(o0[0], o0[1], o0[2], o0[3]);
             *(uint4*)(dx + r1 * C + ch * 8) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
         }
-    }
-    block_sum_add<TPB>(loss, acc * inv);
+    } while (TAP && (row += gridDim.y) < NR);
+    if constexpr (TAP) block_sum_add<TPB>(loss, acc * inv);
 }
 
 __global__ __launch_bounds__(TPB) void nchw_to_nhwc_kernel(const float* __restrict__ x, int C, int HW,
@@ -1354,26 +1279,38 @@ extern "C" int irgan_maxpool_fwd(const void* x, int32_t dt, int32_t N, int32_t H
     return 0;
 }
 
+// The pool backward's dispatch: the rows kernel for the bf16 VGG pools, else the 8-wide or the
+// scalar generic kernel.  Plain: one block row per pooled row; TAP: about 2048 blocks stride over them.
+template <bool TAP>
+static void maxpool_bwd_launch(const void* x, const void* xr, const void* dy, int32_t dt, int32_t N, int32_t H,
+                               int32_t W, int32_t C, void* dx, int32_t relu_mask, float w, double* loss,
+                               irgan_stream_t s) {
+    static const bool rows = !getenv("IRGAN_NO_POOL_ROWS");
+    hipStream_t st = (hipStream_t)s;
+    const long count = (long)N * H * W * C;
+    const int NR = N * (H / 2);   // pooled rows
+    auto grid = [NR](int gx) { return dim3(gx, TAP ? std::max(1, std::min(NR, 2048 / gx)) : NR); };
+    if (rows && dt == IRGAN_BF16 && (C == 64 || C == 128 || C == 256)) {
+        const int ppb = (TPB / 64) * (64 / (2 * (C / 8)));   // pooled pixels per block
+        auto k = C == 64 ? maxpool_bwd_rows_kernel<8, TAP>
+                         : C == 128 ? maxpool_bwd_rows_kernel<16, TAP> : maxpool_bwd_rows_kernel<32, TAP>;
+        k<<<grid(irgan_cdiv(W / 2, ppb)), TPB, 0, st>>>((const bf16_t*)x, (const bf16_t*)xr, (const bf16_t*)dy, H, W,
+                                                        (bf16_t*)dx, relu_mask, w, count, NR, loss);
+    } else if (C % 8 == 0) {
+        maxpool_bwd_kernel<8, TAP><<<grid(irgan_cdiv((long)(W / 2) * (C / 8), TPB)), TPB, 0, st>>>(
+            x, xr, dy, dt, H, W, C, dx, relu_mask, w, count, NR, loss);
+    } else {
+        maxpool_bwd_kernel<1, TAP><<<grid(irgan_cdiv((long)(W / 2) * C, TPB)), TPB, 0, st>>>(
+            x, xr, dy, dt, H, W, C, dx, relu_mask, w, count, NR, loss);
+    }
+}
+
 extern "C" int irgan_maxpool_bwd(const void* x, const void* dy, int32_t dt, int32_t N, int32_t H, int32_t W, int32_t C,
                                  void* dx, int32_t relu_mask, irgan_stream_t s) {
     long total = (long)N * (H / 2) * (W / 2) * C;
     RS_CHECK(total);
     if ((long)N * (H / 2) > 65535) return IRGAN_EUNSUPPORTED;
-    static const bool rows = !getenv("IRGAN_NO_POOL_ROWS");
-    if (rows && dt == IRGAN_BF16 && (C == 64 || C == 128 || C == 256)) {
-        const int ppb = (TPB / 64) * (64 / (2 * (C / 8)));   // pooled pixels per block
-        dim3 g(irgan_cdiv(W / 2, ppb), N * (H / 2));
-        const bf16_t *xp = (const bf16_t*)x, *gp = (const bf16_t*)dy;
-        if (C == 64) maxpool_bwd_rows_kernel<8><<<g, TPB, 0, (hipStream_t)s>>>(xp, gp, H, W, (bf16_t*)dx, relu_mask);
-        else if (C == 128) maxpool_bwd_rows_kernel<16><<<g, TPB, 0, (hipStream_t)s>>>(xp, gp, H, W, (bf16_t*)dx, relu_mask);
-        else maxpool_bwd_rows_kernel<32><<<g, TPB, 0, (hipStream_t)s>>>(xp, gp, H, W, (bf16_t*)dx, relu_mask);
-    } else if (C % 8 == 0) {
-        dim3 g(irgan_cdiv((long)(W / 2) * (C / 8), TPB), N * (H / 2));
-        maxpool_bwd_kernel<8><<<g, TPB, 0, (hipStream_t)s>>>(x, dy, dt, H, W, C, dx, relu_mask);
-    } else {
-        dim3 g(irgan_cdiv((long)(W / 2) * C, TPB), N * (H / 2));
-        maxpool_bwd_kernel<1><<<g, TPB, 0, (hipStream_t)s>>>(x, dy, dt, H, W, C, dx, relu_mask);
-    }
+    maxpool_bwd_launch<false>(x, nullptr, dy, dt, N, H, W, C, dx, relu_mask, 0.f, nullptr, s);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }
@@ -1383,26 +1320,8 @@ extern "C" int irgan_maxpool_bwd_tap(const void* x, const void* xr, const void* 
     if (dt != IRGAN_F32 && dt != IRGAN_BF16) return IRGAN_EINVAL;
     // an odd side leaves a last row / column outside every window, which the tap still needs
     if (H % 2 || W % 2 || (long)N * (H / 2) > 65535) return IRGAN_EUNSUPPORTED;
-    const long count = (long)N * H * W * C;
-    RS_CHECK(count);
-    static const bool rows = !getenv("IRGAN_NO_POOL_ROWS");
-    hipStream_t st = (hipStream_t)s;
-    const int NR = N * (H / 2);   // pooled rows; about 2048 blocks stride over them
-    auto grid = [NR](int gx) { return dim3(gx, std::max(1, std::min(NR, 2048 / gx))); };
-    if (rows && dt == IRGAN_BF16 && (C == 64 || C == 128 || C == 256)) {
-        const int ppb = (TPB / 64) * (64 / (2 * (C / 8)));   // pooled pixels per block
-        const dim3 g = grid(irgan_cdiv(W / 2, ppb));
-        const bf16_t *xp = (const bf16_t*)x, *rp = (const bf16_t*)xr, *gp = (const bf16_t*)dy;
-        if (C == 64) maxpool_bwd_tap_rows_kernel<8><<<g, TPB, 0, st>>>(xp, rp, gp, H, W, (bf16_t*)dx, w, count, NR, loss);
-        else if (C == 128) maxpool_bwd_tap_rows_kernel<16><<<g, TPB, 0, st>>>(xp, rp, gp, H, W, (bf16_t*)dx, w, count, NR, loss);
-        else maxpool_bwd_tap_rows_kernel<32><<<g, TPB, 0, st>>>(xp, rp, gp, H, W, (bf16_t*)dx, w, count, NR, loss);
-    } else if (C % 8 == 0) {
-        maxpool_bwd_tap_kernel<8><<<grid(irgan_cdiv((long)(W / 2) * (C / 8), TPB)), TPB, 0, st>>>(
-            x, xr, dy, dt, H, W, C, dx, w, count, NR, loss);
-    } else {
-        maxpool_bwd_tap_kernel<1><<<grid(irgan_cdiv((long)(W / 2) * C, TPB)), TPB, 0, st>>>(
-            x, xr, dy, dt, H, W, C, dx, w, count, NR, loss);
-    }
+    RS_CHECK((long)N * H * W * C);
+    maxpool_bwd_launch<true>(x, xr, dy, dt, N, H, W, C, dx, 1, w, loss, s);
     IRGAN_LAUNCH_CHECK();
     return 0;
 }

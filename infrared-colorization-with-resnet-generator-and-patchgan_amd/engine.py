@@ -118,7 +118,21 @@ def d_param_shapes(input_nc=4, ndf=64, n_layers=3, use_bias=True, batch_norm=Fal
     return s
 
 
-VGG_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256))
+class VGGConv(NamedTuple):
+    """One conv + ReLU of vgg16.features[:16]."""
+    index: int    # torchvision's index of the conv in vgg16.features (its ReLU is index + 1)
+    relu: str     # torchvision's name of its ReLU map
+    cin: int
+    cout: int
+    pool: bool    # MaxPool2d(2) follows the ReLU
+
+
+# the one description of the stack; everything below that names a VGG layer is derived from it
+VGG_STACK = (VGGConv(0, "relu1_1", 3, 64, False), VGGConv(2, "relu1_2", 64, 64, True),
+             VGGConv(5, "relu2_1", 64, 128, False), VGGConv(7, "relu2_2", 128, 128, True),
+             VGGConv(10, "relu3_1", 128, 256, False), VGGConv(12, "relu3_2", 256, 256, False),
+             VGGConv(14, "relu3_3", 256, 256, False))
+VGG_CONVS = tuple((c.index, c.cin, c.cout) for c in VGG_STACK)
 
 
 def vgg_param_shapes():
@@ -1429,8 +1443,8 @@ NO_POOL_FUSION = bool(os.environ.get("IRGAN_NO_POOL_FUSION"))   # A/B: separate 
 NO_TAP_FUSION = bool(os.environ.get("IRGAN_NO_TAP_FUSION"))     # A/B: maxpool_bwd, then the tap as its own launch
 
 # Config.perc_layers: torchvision's names of the ReLU maps of vgg16.features[:16]; the index is the
-# engine's conv number j (relu1_2 = 1 and relu2_2 = 3 feed the two MaxPool2d)
-PERC_LAYERS = ("relu1_1", "relu1_2", "relu2_1", "relu2_2", "relu3_1", "relu3_2", "relu3_3")
+# engine's conv number j
+PERC_LAYERS = tuple(c.relu for c in VGG_STACK)
 DEFAULT_TAPS = (("relu3_3", 1.0),)   # the reference's perceptual term (ir:1667-1669)
 
 
@@ -1493,59 +1507,69 @@ class VGGEngine:
         backward_taps reads it."""
         g, T = bufs or self.bufs, self.tdt
         x = vin
-        acts = g.state["acts"] = [vin]
+        acts = g.state["acts"] = []   # per conv j run: (its input map, its ReLU output)
         sl = (lambda f: f) if part is None else (lambda f: f.batch(*part))  # noqa: E731
         tapped = () if taps is None else [PERC_LAYERS.index(n) for n, _ in taps]
         last = max(tapped, default=len(self.packs) - 1)
         for j, pc in enumerate(self.packs[:last + 1]):
             y = Feat(g.get(f"v{j}", (x.N, x.H, x.W, pc.spec.cout), T))
-            pooled = j in (1, 3) and j < last
-            if pooled:   # conv -> ReLU -> MaxPool2d(2) (ir:664), fused where a kernel takes the layer
+            acts.append((x, y))
+            if VGG_STACK[j].pool and j < last:
+                # conv -> ReLU -> MaxPool2d(2) (ir:664), fused where a kernel takes the layer
                 p = Feat(g.get(f"p{j}", (x.N, x.H // 2, x.W // 2, pc.spec.cout), T))
                 full = keep or j in tapped
                 if NO_POOL_FUSION or not ops.conv_fwd_pool(pc, sl(x), sl(y) if full else None, sl(p)):
                     ops.conv_fwd(pc, sl(x), sl(y), act=ACT_RELU)
                     ops.maxpool(sl(y), sl(p))
+                x = p
             else:
                 ops.conv_fwd(pc, sl(x), sl(y), act=ACT_RELU)
-            acts.append(y)
-            x = y
-            if pooled:
-                acts.append(p)
-                x = p
+                x = y
         return x
+
+    def _tap(self, g, nb, j, w, dz, loss, accumulate):
+        """The perceptual term of conv j's ReLU map (fake images [0, nb), real images [nb, 2 nb)) at
+        weight w: its value into ``loss``, its gradient written or added to dz."""
+        y = g.state["acts"][j][1]
+        ops.l1_tap(y.batch(0, nb).t, y.batch(nb, nb).t, w, dz.t, loss, accumulate)
+
+    def _walk(self, g, nb, top, dz, wt=(), loss=None) -> Feat:
+        """The backward-data walk from dz = dL/d(conv ``top``'s pre-activation) of the first nb
+        images down to d(input).  wt ({conv j: weight}, with ``loss``): the perceptual taps below
+        ``top``, each added to the dz of its layer on the way down."""
+        T, acts = self.tdt, g.state["acts"]
+        for j in range(top, 0, -1):
+            pc, xin, below = self.packs[j], acts[j][0].batch(0, nb), acts[j - 1][1]   # below: conv j-1's ReLU map
+            src = below.batch(0, nb)
+            dzn = Feat(g.get(f"dz{j - 1}", (nb, src.H, src.W, src.C), T))
+            tap = j - 1 in wt
+            if VGG_STACK[j - 1].pool:  # input is a pool output: dgrad -> maxpool bwd (+relu') of the pool input
+                dp = Feat(g.get(f"dp{j}", (nb, xin.H, xin.W, xin.C), T))
+                ops.conv_dgrad(pc, dz, dp)
+                real = below.batch(nb, nb) if tap else None
+                if tap and not NO_TAP_FUSION and ops.maxpool_bwd_tap(src, real, dp, dzn, wt[j - 1], loss):
+                    tap = False   # applied inside the pool backward
+                else:
+                    if src.H % 2 or src.W % 2:   # floor pooling: the last odd row / column gets no gradient
+                        dzn.t.zero_()
+                    ops.maxpool_bwd(src, dp, dzn, relu_mask=True)
+            else:  # input is a ReLU output: fold relu' into the dgrad epilogue
+                ops.conv_dgrad(pc, dz, dzn, mask=xin, mask_act=1)
+            if tap:
+                self._tap(g, nb, j - 1, wt[j - 1], dzn, loss, True)
+            dz = dzn
+        vin = acts[0][0]
+        dvin = Feat(g.get("dvin", (nb, vin.H, vin.W, self.packs[0].spec.cin), torch.float32))
+        ops.conv_dgrad(self.packs[0], dz, dvin)
+        return dvin
 
     def backward_input(self, dfeat: Feat, nb: int, bufs: Buffers = None) -> Feat:
         """d(input) for the first nb images (frozen weights: backward-data only).
         dfeat = dL/d(relu3_3 output) for those images."""
-        g, T = bufs or self.bufs, self.tdt
-        acts = [a.batch(0, nb) for a in g.state["acts"]]
-        # acts: [vin, v0, v1, p1, v2, v3, p3, v4, v5, v6]
-        out_of = {0: 1, 1: 2, 2: 4, 3: 5, 4: 7, 5: 8, 6: 9}     # conv j output index in acts
-        in_of = {0: 0, 1: 1, 2: 3, 3: 4, 4: 6, 5: 7, 6: 8}      # conv j input index in acts
-        dz = Feat(g.get("dz6", tuple(dfeat.t.shape), T))
-        ops.act_bwd(dfeat, acts[out_of[6]], ACT_RELU, dz)
-        for j in reversed(range(len(self.packs))):
-            pc = self.packs[j]
-            xin = acts[in_of[j]]
-            if j == 0:
-                dvin = Feat(g.get("dvin", (nb, xin.H, xin.W, pc.spec.cin), torch.float32))
-                ops.conv_dgrad(pc, dz, dvin)
-                return dvin
-            prev = in_of[j]
-            if prev in (3, 6):  # input is a pool output: dgrad -> maxpool bwd (+relu') of the pool input
-                dp = Feat(g.get(f"dp{j}", (nb, xin.H, xin.W, xin.C), T))
-                ops.conv_dgrad(pc, dz, dp)
-                src = acts[prev - 1]
-                dzn = Feat(g.get(f"dz{j - 1}", (nb, src.H, src.W, src.C), T))
-                if src.H % 2 or src.W % 2:   # floor pooling: the last odd row / column gets no gradient
-                    dzn.t.zero_()
-                ops.maxpool_bwd(src, dp, dzn, relu_mask=True)
-            else:  # input is a ReLU output: fold relu' into the dgrad epilogue
-                dzn = Feat(g.get(f"dz{j - 1}", (nb, xin.H, xin.W, xin.C), T))
-                ops.conv_dgrad(pc, dz, dzn, mask=xin, mask_act=1)
-            dz = dzn
-        return None
+        g, top = bufs or self.bufs, len(self.packs) - 1
+        dz = Feat(g.get(f"dz{top}", tuple(dfeat.t.shape), self.tdt))
+        ops.act_bwd(dfeat, g.state["acts"][top][1].batch(0, nb), ACT_RELU, dz)
+        return self._walk(g, nb, top, dz)
 
     def backward_taps(self, taps, nb: int, scale: float, loss: torch.Tensor, bufs: Buffers = None) -> Feat:
         """The multi-layer perceptual term (Config.perc_layers) after forward(..., taps=taps) ran on
@@ -1555,47 +1579,13 @@ class VGGEngine:
         shallower tap adds its gradient to the dz of its layer on the way down: a tapped pool input
         inside the pool backward (ops.maxpool_bwd_tap; NO_TAP_FUSION or a refused shape: maxpool_bwd,
         then l1_tap over the whole map), any other layer by l1_tap on what the dgrad epilogue wrote."""
-        g, T = bufs or self.bufs, self.tdt
-        fake = [a.batch(0, nb) for a in g.state["acts"]]
-        real = [a.batch(nb, nb) for a in g.state["acts"]]
-        out_of = {0: 1, 1: 2, 2: 4, 3: 5, 4: 7, 5: 8, 6: 9}     # conv j output index in acts
-        in_of = {0: 0, 1: 1, 2: 3, 3: 4, 4: 6, 5: 7, 6: 8}      # conv j input index in acts
+        g = bufs or self.bufs
         wt = {PERC_LAYERS.index(n): scale * w for n, w in taps}
-
-        def tap(j, dz, accumulate):
-            ops.l1_tap(fake[out_of[j]].t, real[out_of[j]].t, wt[j], dz.t, loss, accumulate)
-
         top = max(wt)
-        src = fake[out_of[top]]
-        dz = Feat(g.get(f"dz{top}", (nb, src.H, src.W, src.C), T))
-        tap(top, dz, False)
-        for j in range(top, -1, -1):
-            pc = self.packs[j]
-            xin = fake[in_of[j]]
-            if j == 0:
-                dvin = Feat(g.get("dvin", (nb, xin.H, xin.W, pc.spec.cin), torch.float32))
-                ops.conv_dgrad(pc, dz, dvin)
-                return dvin
-            prev = in_of[j]
-            if prev in (3, 6):  # input is a pool output: dgrad -> maxpool bwd (+relu') of the pool input
-                dp = Feat(g.get(f"dp{j}", (nb, xin.H, xin.W, xin.C), T))
-                ops.conv_dgrad(pc, dz, dp)
-                src = fake[prev - 1]
-                dzn = Feat(g.get(f"dz{j - 1}", (nb, src.H, src.W, src.C), T))
-                if j - 1 not in wt or NO_TAP_FUSION or \
-                        not ops.maxpool_bwd_tap(src, real[prev - 1], dp, dzn, wt[j - 1], loss):
-                    if src.H % 2 or src.W % 2:   # floor pooling: the last odd row / column gets no gradient
-                        dzn.t.zero_()
-                    ops.maxpool_bwd(src, dp, dzn, relu_mask=True)
-                    if j - 1 in wt:
-                        tap(j - 1, dzn, True)
-            else:  # input is a ReLU output: fold relu' into the dgrad epilogue
-                dzn = Feat(g.get(f"dz{j - 1}", (nb, xin.H, xin.W, xin.C), T))
-                ops.conv_dgrad(pc, dz, dzn, mask=xin, mask_act=1)
-                if j - 1 in wt:
-                    tap(j - 1, dzn, True)
-            dz = dzn
-        return None
+        src = g.state["acts"][top][1]
+        dz = Feat(g.get(f"dz{top}", (nb, src.H, src.W, src.C), self.tdt))
+        self._tap(g, nb, top, wt[top], dz, loss, False)
+        return self._walk(g, nb, top, dz, wt, loss)
 
 
 # ----------------------------------------------------------------------------

@@ -35,8 +35,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import (Buffers, DiscriminatorEngine, GANStep, GeneratorEngine, ParamStore, VGGEngine, d_layers,
-                     d_param_shapes, g_param_shapes, perc_taps, res_conv_keys, vgg_param_shapes)
+from .engine import (VGG_STACK, Buffers, DiscriminatorEngine, GANStep, GeneratorEngine, ParamStore, VGGEngine,
+                     d_layers, d_param_shapes, g_param_shapes, perc_taps, res_conv_keys, vgg_param_shapes)
 from .ops import BF16, F32, Feat
 
 __all__ = ["Config", "Identity", "get_norm_layer", "init_weights", "init_net", "get_lr_lambda", "get_filter",
@@ -495,6 +495,15 @@ class NLayerDiscriminator(_StoreModule):
 # 6) Perceptual / TV / SSIM losses (ir:642-750)
 # =============================================================================
 
+def _dv_to_image_grad(dv, engine):
+    """VGGEngine's d(input) (NHWC, of the normalised image) as the NCHW gradient of the image."""
+    dimg = torch.zeros(dv.N, dv.H, dv.W, dv.C, device=dv.t.device)
+    ops.affine(dv, engine.scale, None, Feat(dimg))
+    out = torch.empty(dv.N, dv.C, dv.H, dv.W, device=dv.t.device)
+    ops.nhwc_to_nchw(Feat(dimg), out)
+    return out
+
+
 class _VFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod):
@@ -509,12 +518,7 @@ class _VFn(torch.autograd.Function):
         mod, bufs = ctx.mod, ctx.bufs
         ctx.bufs = None
         dn = dfeat.permute(0, 2, 3, 1).contiguous().to(mod.engine.tdt)
-        dv = mod.engine.backward_input(Feat(dn), ctx.n, bufs=bufs)
-        dimg = torch.zeros(dv.N, dv.H, dv.W, dv.C, device=dfeat.device)
-        ops.affine(dv, mod.engine.scale, None, Feat(dimg))
-        out = torch.empty(dv.N, dv.C, dv.H, dv.W, device=dfeat.device)
-        ops.nhwc_to_nchw(Feat(dimg), out)
-        return out, None
+        return _dv_to_image_grad(mod.engine.backward_input(Feat(dn), ctx.n, bufs=bufs), mod.engine), None
 
 
 class VGGPerceptual(_StoreModule):
@@ -535,10 +539,8 @@ class VGGPerceptual(_StoreModule):
             sd = {k[len("features."):] if k.startswith("features.") else k: v for k, v in sd.items()}
             self.store.load(sd, strict=True)
         S = self.store
-        mods = []
-        for i in range(16):
-            mods.append(_Slot(S, str(i)) if f"{i}.weight" in S.shapes else None)
-        self.features = _seq(*mods)
+        convs = {c.index for c in VGG_STACK}   # features[: last conv's ReLU + 1]; only the convs hold weights
+        self.features = _seq(*[_Slot(S, str(i)) if i in convs else None for i in range(VGG_STACK[-1].index + 2)])
         for p in self.features.parameters():
             p.requires_grad = False
         self.register_buffer("mean", torch.tensor([0.485, 0.456, 0.406], device=device).view(1, 3, 1, 1))
@@ -695,12 +697,7 @@ class _PercFn(torch.autograd.Function):
         eng.forward(vin, bufs=bufs, part=(B, B), keep=False, taps=taps)
         eng.forward(vin, bufs=bufs, part=(0, B), taps=taps)
         loss = torch.zeros(1, dtype=torch.float64, device=fake.device)
-        dv = eng.backward_taps(taps, B, 1.0, loss, bufs=bufs)
-        dimg = torch.zeros(dv.N, dv.H, dv.W, dv.C, device=fake.device)
-        ops.affine(dv, eng.scale, None, Feat(dimg))
-        grad = torch.empty(dv.N, dv.C, dv.H, dv.W, device=fake.device)
-        ops.nhwc_to_nchw(Feat(dimg), grad)
-        ctx.save_for_backward(grad)
+        ctx.save_for_backward(_dv_to_image_grad(eng.backward_taps(taps, B, 1.0, loss, bufs=bufs), eng))
         return loss.float()[0]
 
     @staticmethod

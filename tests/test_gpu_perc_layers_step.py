@@ -273,3 +273,29 @@ def test_no_tap_fusion_is_the_same_step(monkeypatch, restore_deterministic):
     assert torch.equal(dv0, dv1) and torch.equal(df0, df1)
     assert dv0.abs().max().item() > 0
     assert abs(l0 - l1) <= LC.R_ACC * abs(l0)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_backward_input_and_backward_taps_are_one_walk(dtype):
+    """VGGEngine's two public backwards are one walk under two seeds: after one forward of a 2+2
+    batch (24x40, so the maps 24x40, 12x20 and 6x10 are all even), ops.l1 into dfeat followed by
+    backward_input and backward_taps(DEFAULT_TAPS) give the same dvin -- value equality: the seeds
+    differ only in the sign of their zeros -- and the same loss within R_ACC."""
+    irc = pkg()
+    ops, B = irc.ops, 2
+    vgg = irc.VGGPerceptual(DEV, compute_dtype=dtype)
+    vgg.store.load(seeded()[2], strict=True)
+    vgg.repack()
+    eng = vgg.engine
+    both = torch.cat([batch(seed=13, size=(24, 40))[1], batch(seed=14, size=(24, 40))[1]]).to(DEV)
+    feat = eng.forward(irc.ir_colorization._nhwc_input(both, eng.packs[0], eng.tdt, eng.scale, eng.shift))
+    assert (feat.N, feat.H, feat.W) == (2 * B, 6, 10)
+    loss_a, loss_b = (torch.zeros(1, dtype=torch.float64, device=DEV) for _ in range(2))
+    dfeat = torch.empty_like(feat.t[:B])
+    ops.l1(feat.t[:B], feat.t[B:], 1.0, dfeat, loss_a)
+    dv_a = eng.backward_input(ops.Feat(dfeat), B).t.clone()
+    dv_b = eng.backward_taps(irc.engine.DEFAULT_TAPS, B, 1.0, loss_b).t.clone()
+    print("ONE WALK", dtype, "loss", loss_a.item(), loss_b.item(), "max|dvin|", dv_a.abs().max().item())
+    assert torch.equal(dv_a, dv_b)
+    assert dv_a.abs().max().item() > 0
+    assert abs(loss_a.item() - loss_b.item()) <= LC.R_ACC * abs(loss_a.item())

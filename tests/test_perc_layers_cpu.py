@@ -28,6 +28,19 @@ def test_layer_names_are_torchvisions_relu_positions():
     assert pkg().engine.PERC_LAYERS == ALL
 
 
+def test_vgg_stack_derives_todays_values():
+    """VGG_CONVS, PERC_LAYERS and vgg_param_shapes() are derived from engine.VGG_STACK; pinned
+    here to literals (checkpoints, the oracle and torchvision's state_dict depend on them)."""
+    eng = pkg().engine
+    assert eng.VGG_CONVS == ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256),
+                             (14, 256, 256))
+    assert eng.PERC_LAYERS == ("relu1_1", "relu1_2", "relu2_1", "relu2_2", "relu3_1", "relu3_2", "relu3_3")
+    assert list(eng.vgg_param_shapes()) == ["0.weight", "0.bias", "2.weight", "2.bias", "5.weight", "5.bias",
+                                            "7.weight", "7.bias", "10.weight", "10.bias", "12.weight", "12.bias",
+                                            "14.weight", "14.bias"]
+    assert [c.relu for c in eng.VGG_STACK if c.pool] == ["relu1_2", "relu2_2"]
+
+
 def test_exports():
     irc = pkg()
     assert "perceptual_loss" in irc.ir_colorization.__all__

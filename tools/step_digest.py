@@ -22,6 +22,7 @@ import types
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "infrared-colorization-with-resnet-generator-and-patchgan_amd"
 
+PERC_THREE = dict(perc_layers=("relu1_2", "relu2_2", "relu3_3"), perc_weights=(1.0, 0.5, 0.25))
 # name -> (steps, B, H, W, Config overrides, generator overrides outside Config)
 CASES = {
     "bf16": (3, 2, 64, 64, {}, {}),
@@ -37,6 +38,9 @@ CASES = {
     "dropout": (2, 2, 64, 64, {}, dict(use_dropout=True)),
     "no_antialias": (2, 2, 64, 64, dict(no_antialias=True), {}),
     "no_antialias_up": (2, 2, 64, 64, dict(no_antialias_up=True), {}),
+    # VGGEngine.backward_taps: a tap fused into each pool backward (IRGAN_NO_TAP_FUSION=1: unfused)
+    "perc_three": (2, 2, 64, 64, PERC_THREE, {}),
+    "perc_three_fp32": (2, 2, 64, 64, dict(PERC_THREE, compute_dtype="fp32"), {}),
 }
 
 
